@@ -12,17 +12,27 @@ set (what /root/reference/pretrain.py:278-283,335-336 does with mp.spawn + a tcp
 exits non-zero if any rank failed.  Under `python -m torch.distributed.run ... bench.py --gpus N` (WORLD_SIZE already set)
 the process is a rank and runs directly.
 
-Prints ONE JSON line on rank 0 (see the driver contract): value = whole-job clips/s; plus
+Prints ONE JSON line on rank 0 (see the driver contract): value = whole-job clips/s, ms_per_step = milliseconds of one timed step;
+plus, from the timed steps themselves,
+  steps_ms     — p50 / min / max / p90 of the GPU-side per-step intervals + the host's enqueue time per step;
+  comm_ms      — N > 1: per-step stall of this rank's compute stream behind each collective.
+A plain run does only that: set-up, warm-up, the timed steps, --dump-outputs DIR if given, the line.  Everything measured beyond the
+headline runs with --full only (off by default):
   roofline     — the conv MFMA launches grouped by the kernel template the library dispatched (rsp_conv3d_kernel_name):
                  algorithmic FLOPs / HIP-event time on the launch stream against the fp32-input MFMA peak (157.3 TFLOP/s,
                  MI355X_MICROARCH.md); the block's headline is the kernel with the largest share of the step for THIS arch;
   cpu_baseline — the oracle restatement (oracle/restatement.py, proven equal to the reference) timed on this host's
-                 physical cores on BASELINE config 1 (32 clips; 1 warm-up + 2 timed steps) — rank 0, N=1 only;
+                 physical cores (at most OMP_NUM_THREADS) on BASELINE config 1 (32 clips; 1 warm-up + 2 timed steps) — rank 0, N=1 only;
   parity       — the CPU leg's warm-up step REPLAYS the GPU run's first step (same pre-step state, clips, permutations):
                  relative errors of loss / logits / features / queue slab / whole gradient at the measured size;
-  steps_ms     — p50 / min / max / p90 of the GPU-side per-step intervals + the host's enqueue time per step;
-  comm_ms      — N > 1: per-step stall of this rank's compute stream behind each collective;
-  other_workloads — N = 1 default run: BASELINE configs 3-5 (R3D-18, R(2+1)D B=32; S3D-G B=16 at 224^2), 10 + 30 steps each.
+  hbm_kernels, issued_eagerly, lanes_overlap_main, host_issue_idle_gpu — the streaming kernels against the HBM roofline, the step
+                 issued eagerly after a graphed run, the side-stream overlap probe, the host's issue time on an idle GPU;
+  other_workloads — N = 1 C3D run: BASELINE configs 3-5 (R3D-18, R(2+1)D B=32; S3D-G B=16 at 224^2), 10 + 30 steps each.
+
+--dump-outputs DIR writes what the last timed step computed (losses, logits, the updated queue, a fixed sample of both encoders'
+updated parameters) as DIR/<name>.npy in float32: the state and clips are seeded, so two builds run with the same arguments can be
+compared output for output.  A plain and a --full run of the same arguments take the same steps before the timed region, so they
+dump the same outputs and report the same final_loss.
 """
 import argparse
 import json
@@ -62,7 +72,7 @@ def parse_args(argv=None):
                          "issue the step fast enough (measured in the warm-up: S3D-G's 1 800 launches) — replayed, a step the host "
                          "keeps ahead of is 0.5-2.4 %% slower than issued eagerly with its side streams; on: always; off: never")
     ap.add_argument("--no-other-workloads", dest="other_workloads", action="store_false",
-                    help="skip BASELINE configs 3-5 (R3D-18, R(2+1)D, S3D-G) that the default N=1 C3D run appends")
+                    help="skip BASELINE configs 3-5 (R3D-18, R(2+1)D, S3D-G) that a --full N=1 C3D run appends")
     ap.add_argument("--other-steps", type=int, default=30)
     ap.add_argument("--other-warmup", type=int, default=10)
     ap.add_argument("--deadline", type=float, default=float(os.environ.get("RSP_BENCH_DEADLINE", 1500)),
@@ -80,6 +90,12 @@ def parse_args(argv=None):
     ap.add_argument("--eager-steps", type=int, default=10,
                     help="N=1 graphed runs: also time this many eagerly issued steps (the way N > 1 issues them) after the timed region")
     ap.add_argument("--seed", type=int, default=1234, help="seed of the synthetic state and clips (the default run's is 1234)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and HBM passes, idle-GPU issue samples, eagerly issued "
+                         "steps, the side-stream probe, the CPU baseline with its parity replay, and (N=1 C3D) the other workloads and "
+                         "the data-parallel path at one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--selftest-hang-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--selftest-parity", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--selftest-cpu", action="store_true",
@@ -143,7 +159,8 @@ def launch(n: int, argv, deadline_s: float) -> int:
 # CPU baseline (checker code, never the product path)
 # ----------------------------------------------------------------------------------------------------------------------
 def host_cpu():
-    """(model string, physical cores usable by this process)."""
+    """(model string, physical cores usable by this process — no more than OMP_NUM_THREADS where that is set: a shared host grants a
+    job that many CPUs, and a pool sized by the whole machine only slows itself down)."""
     model, pairs, phys, core = "unknown", set(), None, None
     try:
         with open("/proc/cpuinfo") as f:
@@ -161,7 +178,9 @@ def host_cpu():
     except OSError:
         pass
     avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    return model, max(1, min(len(pairs) or avail, avail))
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    granted = int(omp) if omp.isdigit() and int(omp) > 0 else avail
+    return model, max(1, min(len(pairs) or avail, avail, granted))
 
 
 def rank_cpu_set(local_rank: int, local_ws: int):
@@ -364,8 +383,35 @@ def _pct(xs, q):
     return xs[min(len(xs) - 1, int(round(q * (len(xs) - 1))))] if xs else None
 
 
-def measure(args, arch, B, hw, base_lr, steps, warmup, dev, rank, ws, want_parity=False):
-    """Build the pretext model of `arch`, run `warmup` untimed + `steps` timed steps, return (result dict, parity capture)."""
+DUMP_MAX_ELEMS = 1 << 21         # per array (8 MB of float32): the queue at K = 16384 whole; at most 7 arrays of this size + 3 losses
+
+
+def _dump_arrays(out, inner, seed=0):
+    """What one step hands its caller, as float32 numpy arrays: the three losses, the InfoNCE logits of both views, the ranking
+    logits, and the state the step updated in place (the queue; both encoders' parameters).  An array above DUMP_MAX_ELEMS elements
+    is replaced by a fixed sample of that many (indices drawn from `seed`: the same in every run of the same arguments)."""
+    import torch
+    loss, loss_A, loss_M, logits, rl = out[:5]
+    g = torch.Generator().manual_seed(seed)
+
+    def arr(t):
+        t = t.detach().reshape(-1) if t.numel() > DUMP_MAX_ELEMS else t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        return t.float().cpu().numpy()
+
+    def flat(params):
+        return torch.cat([p.detach().reshape(-1) for p in params])
+
+    return {"loss": arr(loss), "loss_A": arr(loss_A), "loss_M": arr(loss_M), "logits1": arr(logits[0]), "logits2": arr(logits[1]),
+            "l_pos_M": arr(rl[0]), "l_neg_M": arr(rl[1]), "queue": arr(inner.queue),
+            "encoder_q_params": arr(flat(inner.encoder_q.parameters())), "encoder_k_params": arr(flat(inner.encoder_k.parameters()))}
+
+
+def measure(args, arch, B, hw, base_lr, steps, warmup, dev, rank, ws, want_parity=False, lead_step=False):
+    """Build the pretext model of `arch`, run `warmup` untimed + `steps` timed steps, return (result dict, parity capture).
+    `lead_step`: take the step the parity capture would take (untimed, in front of the warm-up) even without capturing it."""
     import torch
     import torch.distributed as dist
     from rspnet_amd import ops
@@ -437,6 +483,8 @@ def measure(args, arch, B, hw, base_lr, steps, warmup, dev, rank, ws, want_parit
                            "l_neg_M": rl[1].detach().cpu(), "q_A": q_A.cpu(), "q_M": q_M.cpu(),
                            "queue_slab": inner.queue[:, ptr0:ptr0 + B].cpu()}}
         del loss, loss_A, loss_M, out, rl
+    elif lead_step:
+        step()      # (the same step uncaptured: a plain run follows the training trajectory of a --full one)
 
     for _ in range(warmup):
         step()
@@ -449,7 +497,7 @@ def measure(args, arch, B, hw, base_lr, steps, warmup, dev, rank, ws, want_parit
     gc.freeze()
     fence()
     graphed = stepper is not None and not stepper.disabled and len(stepper.graphs) > 0
-    if graphed and cuda:
+    if graphed and cuda and args.full:
         # where the GPU's time of a replayed step goes: a few steps with an event pair around every graph (outside the timed region)
         stepper.segment_gpu_events = []
         for _ in range(3):
@@ -483,7 +531,8 @@ def measure(args, arch, B, hw, base_lr, steps, warmup, dev, rank, ws, want_parit
     t0 = time.perf_counter()
     for _ in range(steps):
         h0 = time.perf_counter()
-        loss = step()[0]
+        last = step()
+        loss = last[0]
         host.append((time.perf_counter() - h0) * 1e3)       # time the host needs to ENQUEUE a step (it runs ahead of the GPU)
         waits.append(getattr(stepper, "last_wait_s", 0.0) * 1e3 if stepper is not None else 0.0)
         if cuda:
@@ -497,10 +546,13 @@ def measure(args, arch, B, hw, base_lr, steps, warmup, dev, rank, ws, want_parit
     log = []
     comm, inner.comm_log = inner.comm_log, None
     final_loss = float(loss.detach())
+    # (taken before any further step: a replayed graph's outputs are static buffers that the next replay overwrites)
+    outputs = _dump_arrays(last, inner, args.seed) if args.dump_outputs and rank == 0 else None
+    del last
     # what issuing ONE step costs the host when nothing holds it up: the queue is empty at the start of each sample (inside the
     # timed loop a call also waits whenever the hardware queue is full — GPU time, not submission cost)
     idle_issue = []
-    if cuda:
+    if cuda and args.full:
         for _ in range(5):
             fence()
             h0 = time.perf_counter()
@@ -518,12 +570,14 @@ def measure(args, arch, B, hw, base_lr, steps, warmup, dev, rank, ws, want_parit
     if cuda:
         # worst rank's host time to issue one step (Python + launches + collective calls, without the stepper's back-pressure wait):
         # the number that says whether a rank is host-bound
-        hs = torch.tensor([_pct([h - w for h, w in zip(host, waits)], 0.5), _pct(idle_issue, 0.5)], dtype=torch.float64, device=dev)
+        hs = torch.tensor([_pct([h - w for h, w in zip(host, waits)], 0.5)] + ([_pct(idle_issue, 0.5)] if idle_issue else []),
+                          dtype=torch.float64, device=dev)
         if ws > 1:
             dist.all_reduce(hs, op=dist.ReduceOp.MAX)
         res["host_submit_p50_max_over_ranks"] = round(float(hs[0].item()), 3)
-        res["host_issue_idle_gpu_p50_max_over_ranks"] = round(float(hs[1].item()), 3)
-    if graphed and args.eager_steps > 0:
+        if idle_issue:
+            res["host_issue_idle_gpu_p50_max_over_ranks"] = round(float(hs[1].item()), 3)
+    if graphed and args.eager_steps > 0 and args.full:
         # the same step issued eagerly with its side streams — how a run with more than one rank issues it (RCCL collectives are
         # not captured): the N = 1 point of a scaling curve in the N > 1 issue mode
         eager_step()
@@ -533,7 +587,7 @@ def measure(args, arch, B, hw, base_lr, steps, warmup, dev, rank, ws, want_parit
             eager_step()
         fence()
         res["eager_ms_per_step"] = (time.perf_counter() - te) / args.eager_steps * 1e3
-    if cuda:
+    if cuda and args.full:
         # do the side lanes (query pass / second key pass / weight gradients) really run beside the main stream?  (HIP multiplexes
         # streams onto a few hardware queues: rspnet_amd/streams.py measures it)
         from rspnet_amd import streams as _streams
@@ -542,7 +596,7 @@ def measure(args, arch, B, hw, base_lr, steps, warmup, dev, rank, ws, want_parit
         why = stepper.fallback_reason or "not captured within the warm-up steps"
         res["issue_policy" if why.startswith("issued eagerly by policy") else "graph_fallback"] = why
     roof_steps = steps
-    if cuda:
+    if cuda and args.full:
         # roofline pass: the same step issued eagerly ON ONE STREAM with a HIP-event pair around every convolution launch — the
         # kernels' own durations, as rocprofv3's serialised trace reports them; outside the timed region, continuing the same
         # training state (the step's results do not depend on how it is issued)
@@ -674,6 +728,8 @@ def measure(args, arch, B, hw, base_lr, steps, warmup, dev, rank, ws, want_parit
         torch.cuda.synchronize()
         be._ws.clear()
         torch.cuda.empty_cache()
+    if outputs is not None:
+        res["outputs"] = outputs
     return res, capture
 
 
@@ -747,9 +803,17 @@ def run_rank(args):
     B, hw, base_lr = ARCHS[args.arch]
     B = args.batch or B
     hw = args.hw or hw
-    want_cpu = ws == 1 and not args.no_cpu_baseline and (not cpu_selftest or args.selftest_parity)
+    cpu_leg = ws == 1 and not args.no_cpu_baseline and (not cpu_selftest or args.selftest_parity)
+    want_cpu = cpu_leg and args.full
     m, capture = measure(args, args.arch, B, hw, base_lr, args.steps, args.warmup, dev, rank, ws,
-                         want_parity=want_cpu and args.cpu_sample == B)
+                         want_parity=want_cpu and args.cpu_sample == B, lead_step=cpu_leg and args.cpu_sample == B)
+    outputs = m.pop("outputs", None)
+    if outputs is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), a)
+        del outputs
     if rank == 0:
         K, lr = m["K"], m["lr"]
         res = {
@@ -791,10 +855,10 @@ def run_rank(args):
     # size, a shorter run each — whole-step and dominant-kernel roofline fractions next to the headline.  Each runs in a CHILD
     # interpreter of this file (fresh process, started and waited for — never exec'ed into): whatever happens there — an
     # out-of-memory kill, a runtime crash inside a graph capture — cannot take the headline line down with it.
-    if ws == 1 and not cpu_selftest and args.other_workloads and args.arch == "c3d" and not args.batch and not args.hw:
+    if args.full and ws == 1 and not cpu_selftest and args.other_workloads and args.arch == "c3d" and not args.batch and not args.hw:
         def child(arch, extra, steps, warmup):
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--arch", arch, "--steps", str(steps), "--warmup", str(warmup),
-                   "--queue", str(args.queue), "--graph", args.graph, "--no-cpu-baseline", "--no-other-workloads"] + extra
+                   "--queue", str(args.queue), "--graph", args.graph, "--no-cpu-baseline", "--no-other-workloads", "--full"] + extra
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
             if r.returncode != 0 or not lines:

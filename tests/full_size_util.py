@@ -25,6 +25,14 @@ def rel_l2(a, b):
     return float(np.sqrt(((a - b) ** 2).sum()) / max(np.sqrt((b ** 2).sum()), 1e-30))
 
 
+def feeds_train_bn(name, state):
+    """A convolution's bias whose output goes straight into a BatchNorm (C3D: convX -> bnX): the batch mean removes it."""
+    if not name.endswith(".bias"):
+        return False
+    parent, _, leaf = name[:-len(".bias")].rpartition(".")
+    return leaf.startswith("conv") and f"{parent}.bn{leaf[len('conv'):]}.running_mean" in state
+
+
 def full_size_meta(arch, B, HW, K, seed, lr=0.05, fc_type="linear", speed=2):
     return dict(arch=arch, fc_type=fc_type, B=B, HW=HW, K=K, ws=1, seed=seed, lr=lr, speed=speed, T_in=32, m=0.999, T=0.07,
                 sgd_momentum=0.9, weight_decay=1e-4, margin=2.0, A=1.0, M=1.0)
@@ -75,7 +83,9 @@ def step_vs_oracle(arch, B, HW, K, seed, device, threads=None):
         mine = grads[k].astype(np.float64)
         n2, d2 = float(((mine - g) ** 2).sum()), float((g ** 2).sum())
         num, den = num + n2, den + d2
-        if d2 < 1e-8:                       # conv bias in front of train-mode BN: identically zero in exact arithmetic
+        # conv bias in front of train-mode BN: identically zero in exact arithmetic, so both sides hold rounding residue only — at the
+        # full size the oracle's can pass 1e-8 (its CPU thread count sets the summation order), hence the structural test as well
+        if d2 < 1e-8 or feeds_train_bn(k, st):
             assert n2 < 1e-6, k
             continue
         e = (n2 / d2) ** 0.5

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_contract_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-sample", "2", "--cpu-steps", "1",
-                        "--other-steps", "2", "--other-warmup", "1"],
+                        "--other-steps", "2", "--other-warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -86,7 +86,7 @@ def test_bench_prints_one_contract_line():
 
 def test_bench_parity_object_replays_the_first_gpu_step():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--hw", "32", "--queue", "64", "--cpu-sample", "4", "--cpu-steps", "1", "--seed", "4"],
+                        "--hw", "32", "--queue", "64", "--cpu-sample", "4", "--cpu-steps", "1", "--seed", "4", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][0])
@@ -103,8 +103,32 @@ def test_bench_parity_object_replays_the_first_gpu_step():
 
 def test_bench_roofline_is_arch_aware():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--arch", "resnet18", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][0])
     assert "resnet18" in d["metric"] and "cpu_baseline" not in d
     assert d["roofline"]["kernel"].startswith(("igemm_persist_kernel<128, 64", "igemm_kernel<128, 64"))      # R3D-18's layer-1 / stem launches dominate, not <128,128>
+
+
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """The run the driver repeats: headline only (no roofline / CPU leg / other workloads), and --dump-outputs writes what the last
+    timed step computed — float32 arrays within 64 MB, the loss the line reports as final_loss."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["unit"] == "clips/s" and d["steps"] == 3 and d["warmup"] == 2 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) <= 1e-2 * d["value"]
+    for k in ("roofline", "hbm_kernels", "cpu_baseline", "parity", "other_workloads", "dp_path_at_one_rank"):
+        assert k not in d, k
+    total = 0
+    for n in os.listdir(tmp_path):
+        a = np.load(tmp_path / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "logits1.npy").shape == (32, 16385) and np.load(tmp_path / "queue.npy").shape == (128, 16384)
+    assert abs(float(np.load(tmp_path / "loss.npy")) - d["final_loss"]) <= 1e-4 * max(1.0, abs(d["final_loss"]))

@@ -120,7 +120,7 @@ def test_parity_leg_replays_the_first_step():
     """The line's "parity" object: the CPU leg's warm-up step replays the measured run's first step (same state, clips,
     permutations) — run here with the checker backend standing in for the GPU."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--selftest-cpu", "--selftest-parity", "--arch", "c3d", "--batch", "4",
-                        "--cpu-sample", "4", "--cpu-steps", "1", "--hw", "32", "--queue", "64", "--steps", "1", "--warmup", "0"],
+                        "--cpu-sample", "4", "--cpu-steps", "1", "--hw", "32", "--queue", "64", "--steps", "1", "--warmup", "0", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][0])
@@ -147,3 +147,39 @@ def test_bench_under_torch_distributed_run():
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2" and d["scaling"] == "weak" and "comm_ms" in d
+
+
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain run measures the headline only (no CPU leg, no parity replay); --dump-outputs writes what its last timed step computed.
+    The same arguments give the same arrays, and a --full run of them takes the same steps, so it dumps the same arrays as well."""
+    import numpy as np
+    base = [sys.executable, BENCH, "--gpus", "1", "--selftest-cpu", "--selftest-parity", "--arch", "c3d", "--batch", "4",
+            "--cpu-sample", "4", "--cpu-steps", "1", "--hw", "32", "--queue", "64", "--steps", "2", "--warmup", "1"]
+    runs = {}
+    for tag, extra in (("plain", []), ("again", []), ("full", ["--full"])):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=600,
+                           cwd=ROOT, env=_env())
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
+        assert len(lines) == 1, r.stdout
+        runs[tag] = json.loads(lines[0])
+    d = runs["plain"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] - 4 / (d["ms_per_step"] * 1e-3)) <= 1e-2 * d["value"]
+    assert "cpu_baseline" not in d and "parity" not in d
+    assert "cpu_baseline" in runs["full"] and runs["full"]["parity"]["ok"] is True
+    assert d["final_loss"] == runs["again"]["final_loss"] == runs["full"]["final_loss"]
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert {"loss.npy", "loss_A.npy", "loss_M.npy", "logits1.npy", "logits2.npy", "l_pos_M.npy", "l_neg_M.npy", "queue.npy",
+            "encoder_q_params.npy", "encoder_k_params.npy"} == set(names)
+    total = 0
+    for n in names:
+        a = np.load(tmp_path / "plain" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        np.testing.assert_array_equal(a, np.load(tmp_path / "again" / n), err_msg=n)
+        np.testing.assert_array_equal(a, np.load(tmp_path / "full" / n), err_msg=n)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert abs(float(np.load(tmp_path / "plain" / "loss.npy")) - d["final_loss"]) <= 1e-4 * max(1.0, abs(d["final_loss"]))
+    assert np.load(tmp_path / "plain" / "logits1.npy").shape == (4, 65)

@@ -7,7 +7,7 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"; cd "$R"
 for a in "${ARCHS[@]}"; do
   for v in "" 1 "" 1; do
     if [ -z "$v" ]; then unset $VAR; else export $VAR=1; fi
-    python3 bench.py --arch $a --no-cpu-baseline --no-other-workloads --steps 30 --warmup 8 2>/dev/null | python3 -c "
+    python3 bench.py --arch $a --no-cpu-baseline --no-other-workloads --steps 30 --warmup 8 --full 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); r=d['roofline']
 print('$a $VAR=${v:-0}', d['value'], d['ms_per_step'], 'conv ms', r['all_conv_launches']['ms_per_step'], {k:(v['tflops'],v['ms_per_step']) for k,v in list(r['per_kernel'].items())[:4]})"

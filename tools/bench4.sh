@@ -3,7 +3,7 @@
 OUT="gpurun_out/$1"; REPS="${2:-2}"; mkdir -p "$OUT"
 for a in c3d resnet18 r2plus1d-vcop s3dg; do
   for rep in $(seq 1 $REPS); do
-    python bench.py --arch $a --no-cpu-baseline --no-other-workloads > "$OUT/${a}_$rep.json" 2> "$OUT/${a}_$rep.err"
+    python bench.py --arch $a --no-cpu-baseline --no-other-workloads --full > "$OUT/${a}_$rep.json" 2> "$OUT/${a}_$rep.err"
   done
 done
 python - "$OUT" <<'PY'

@@ -1,12 +1,13 @@
 #!/bin/bash
-# Run ON THE GPU BOX: one default-length bench line per BASELINE backbone -> gpurun_out/bench_<tag>_<arch>.json
+# Run ON THE GPU BOX: one default-length bench line (with --full) per BASELINE backbone -> $OUT/bench_<tag>_<arch>.json,
+# OUT = bench_out/ of the repository unless set
 TAG="$1"; shift
 ARCHS=("$@"); [ ${#ARCHS[@]} -eq 0 ] && ARCHS=(c3d resnet18 r2plus1d-vcop s3dg)
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
-mkdir -p "$R/gpurun_out"
+OUT="${OUT:-$R/bench_out}"; mkdir -p "$OUT"
 for a in "${ARCHS[@]}"; do
-  python3 "$R/bench.py" --arch "$a" --no-cpu-baseline > "$R/gpurun_out/bench_${TAG}_$a.json" 2> "$R/gpurun_out/bench_${TAG}_$a.err"
-  python3 - "$R/gpurun_out/bench_${TAG}_$a.json" <<'PY'
+  python3 "$R/bench.py" --arch "$a" --no-cpu-baseline --full > "$OUT/bench_${TAG}_$a.json" 2> "$OUT/bench_${TAG}_$a.err"
+  python3 - "$OUT/bench_${TAG}_$a.json" <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[1])); r = d["roofline"]

@@ -18,15 +18,15 @@ for a in "${ARCHS[@]}"; do
   # are the kernels' own (on side streams / as graph branches a dispatch's interval also holds its neighbours' time) — the same
   # conditions as bench.py's roofline pass, whose avg_launch_ms they must agree with; one counter pass each
   unset RSP_NO_EAGER_OVERLAP
-  python3 "$R/bench.py" --arch "$a" --no-cpu-baseline --no-other-workloads > "$OUT/bench_${TAG}_$a.json" 2> "$OUT/bench_${TAG}_$a.err"
+  python3 "$R/bench.py" --arch "$a" --no-cpu-baseline --no-other-workloads --full > "$OUT/bench_${TAG}_$a.json" 2> "$OUT/bench_${TAG}_$a.err"
   export RSP_NO_EAGER_OVERLAP=1
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${TAG}_$a" -- python3 "$R/bench.py" --arch "$a" --steps 10 --warmup 3 --no-cpu-baseline --no-other-workloads --graph off \
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${TAG}_$a" -- python3 "$R/bench.py" --arch "$a" --steps 10 --warmup 3 --no-cpu-baseline --no-other-workloads --graph off --full \
     > "$OUT/bench_under_rocprof_${TAG}_$a.json" 2> "$OUT/prof_${TAG}_$a.err"
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_${TAG}_$a" -- python3 "$R/bench.py" --arch "$a" --steps 2 --warmup 1 --no-cpu-baseline --no-other-workloads --graph off \
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_${TAG}_$a" -- python3 "$R/bench.py" --arch "$a" --steps 2 --warmup 1 --no-cpu-baseline --no-other-workloads --graph off --full \
     > /dev/null 2> "$OUT/pmc_fetch_${TAG}_$a.err"
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_${TAG}_$a" -- python3 "$R/bench.py" --arch "$a" --steps 2 --warmup 1 --no-cpu-baseline --no-other-workloads --graph off \
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_${TAG}_$a" -- python3 "$R/bench.py" --arch "$a" --steps 2 --warmup 1 --no-cpu-baseline --no-other-workloads --graph off --full \
     > /dev/null 2> "$OUT/pmc_write_${TAG}_$a.err"
-  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc_mfma_${TAG}_$a" -- python3 "$R/bench.py" --arch "$a" --steps 2 --warmup 1 --no-cpu-baseline --no-other-workloads --graph off \
+  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc_mfma_${TAG}_$a" -- python3 "$R/bench.py" --arch "$a" --steps 2 --warmup 1 --no-cpu-baseline --no-other-workloads --graph off --full \
     > /dev/null 2> "$OUT/pmc_mfma_${TAG}_$a.err"
   # keep only the small summaries of the raw traces (the per-dispatch kernel trace of 10 steps is tens of MB)
   find "$OUT/prof_${TAG}_$a" -name '*_kernel_trace.csv' -delete

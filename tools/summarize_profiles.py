@@ -68,7 +68,7 @@ for arch, B in BATCH.items():
         if os.path.exists(src) and os.path.getsize(src):
             shutil.copy(src, f"{out}/{kind}_{arch}_b{B}_{tag}.json")
     fetch_f, write_f, mfma_f = (one(f"{g}/pmc_{k}_{tag}_{arch}/*/*_counter_collection.csv") for k in ("fetch", "write", "mfma"))
-    lines = [f"# {arch} B={B}: rocprofv3 --pmc <counter> -- python3 bench.py --arch {arch} --steps 2 --warmup 1 ({PROFILED_STEPS} steps), "
+    lines = [f"# {arch} B={B}: rocprofv3 --pmc <counter> -- python3 bench.py --arch {arch} --steps 2 --warmup 1 --full ({PROFILED_STEPS} steps), "
              f"one pass per counter group; FETCH x2 per MI355X_MICROARCH.md (gfx950 half-count), KiB -> bytes",
              f"# {'kernel':58s} launches  fetch_MB/launch(x2)  write_MB/launch  hbm_MB/launch  mfma_busy"]
     fetch = pmc_by_kernel(fetch_f) if fetch_f else ({}, {})
