@@ -422,6 +422,25 @@ int rsp_augment_batch(const rsp_augment_clip_desc* descs, int32_t n_clips, int32
                       const float* std3, const float* blur9, float* out, int64_t out_clip_stride, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Video retrieval search (retrieval.hip; the reference's retrieval.py:150-176).
+ * q (Nq x D, row pitch ldq) and g (Ng x D, row pitch ldg): fp32 row-major, D and the pitches even, 8-byte aligned bases.
+ * Writes for every query the k (1..64) nearest gallery rows by cosine distance d = clip(1 - q.g / (|q| |g|), 0, 2), best
+ * first: idx (Nq x k, int32) and dist (Nq x k, fp32).  Ranking: fp32 similarity descending; an exact tie goes to the lower
+ * gallery index.  A zero-norm row has similarity 0 (distance 1) to everything.  When Ng < k the tail slots hold index -1 and
+ * distance +inf.  The Nq x Ng matrix is never stored.  splits: gallery ranges searched by separate workgroups and merged
+ * (<= 0: chosen from the sizes; rsp_cosine_topk_splits tells the count used); the output does not depend on it, bit for bit.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rsp_cosine_topk_splits(int32_t Nq, int32_t Ng, int32_t splits);
+size_t rsp_cosine_topk_workspace(int32_t Nq, int32_t Ng, int32_t D, int32_t k, int32_t splits);
+int rsp_cosine_topk(const float* q, int32_t ldq, int32_t Nq, const float* g, int32_t ldg, int32_t Ng, int32_t D, int32_t k,
+                    int32_t splits, int32_t* idx, float* dist, void* workspace, size_t workspace_bytes, void* stream);
+/* counts[i] = number of queries whose label y_q[row] appears among the labels y_g[idx[row][0 .. ks[i])] (retrieval.py:169-
+ * 176).  idx: the Nq x k output of rsp_cosine_topk (negative entries never hit); y_q / y_g: int64 device labels; ks_host: HOST
+ * array of nks (1..16) values in [1, k], read during the call; counts: nks int32 on the device. */
+int rsp_topk_hits(const int32_t* idx, int32_t Nq, int32_t k, const int64_t* y_q, const int64_t* y_g, int32_t Ng,
+                  const int32_t* ks_host, int32_t nks, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,10 @@ SIGNATURES = {
     "rsp_augment_workspace": (_sz, [_i32, _i32, _i32]),
     "rsp_augment_batch": (C.c_int, [_p, _i32, _i32, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _p, _i64,
                                     _p, _sz, _p]),
+    "rsp_cosine_topk_splits": (_i32, [_i32, _i32, _i32]),
+    "rsp_cosine_topk_workspace": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "rsp_cosine_topk": (C.c_int, [_p, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _sz, _p]),
+    "rsp_topk_hits": (C.c_int, [_p, _i32, _i32, _p, _p, _i32, C.POINTER(C.c_int32), _i32, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

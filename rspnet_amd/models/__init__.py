@@ -57,6 +57,20 @@ class ModelFactory:
             model.train = override_train
         return model
 
+    def build(self, local_rank: int) -> nn.Module:
+        """The bare backbone ``get_model_class(**cfg.model)(num_classes=...)`` on cuda:local_rank (:108-123), wrapped like
+        build_multitask_wrapper: DistributedDataParallel under a process group of more than one rank, else the pass-through
+        holder.  Retrieval calls ``model.module.get_feature(clip)`` on it."""
+        import torch
+        import torch.distributed as dist
+        model_cfg = dict(self._get("model"))
+        model = get_model_class(**model_cfg)(num_classes=int(self._get("dataset.num_classes")))
+        model = self._post_process_model(model)
+        model = model.to(torch.device("cuda", local_rank))
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            return nn.parallel.DistributedDataParallel(model, device_ids=[local_rank])
+        return _SingleProcess(model)
+
     def build_multitask_wrapper(self, local_rank: int) -> nn.Module:
         """MultiTaskWrapper(finetune=True) on cuda:local_rank, wrapped in DistributedDataParallel when a process group is up
         (:125-143); with a single process it is wrapped in a pass-through holder so that ``model.module`` exists either way."""

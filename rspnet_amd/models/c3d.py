@@ -9,6 +9,7 @@ initialisation as the reference); the arithmetic runs through rspnet_amd.engine.
 from torch import nn
 
 from ..engine import ConvBN, Plan
+from .feature import FeatureMixin
 
 # (suffix, Cin, Cout, pool after the block)
 _BLOCKS = (
@@ -23,7 +24,7 @@ _BLOCKS = (
 )
 
 
-class C3D(nn.Module):
+class C3D(FeatureMixin, nn.Module):
     feat_dim = 512
     classifier_names = ("linear",)
 

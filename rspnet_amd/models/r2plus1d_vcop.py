@@ -10,6 +10,7 @@ from torch import nn
 from torch.nn.modules.utils import _triple
 
 from ..engine import ConvBN, Plan
+from .feature import FeatureMixin
 
 
 class SpatioTemporalConv(nn.Module):
@@ -50,7 +51,7 @@ class SpatioTemporalResLayer(nn.Module):
                                      for _ in range(layer_size - 1)])
 
 
-class R2Plus1DNet(nn.Module):
+class R2Plus1DNet(FeatureMixin, nn.Module):
     classifier_names = ("linear",)
 
     def __init__(self, layer_sizes, with_classifier=False, return_conv=False, num_classes=101):

@@ -8,6 +8,7 @@ stride-2 conv + BN shortcut.  Initialisation as the reference: Kaiming-normal(fa
 from torch import nn
 
 from ..engine import ConvBN, Plan, Pool
+from .feature import FeatureMixin
 
 
 def _conv(cin, cout, k, stride=1, padding=0):
@@ -43,7 +44,7 @@ class Bottleneck(nn.Module):
         self.stride = stride
 
 
-class ResNet(nn.Module):
+class ResNet(FeatureMixin, nn.Module):
     classifier_names = ("fc",)
 
     def __init__(self, block, layers, sample_size=112, sample_duration=16, shortcut_type="B", num_classes=400):

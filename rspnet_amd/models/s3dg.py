@@ -11,6 +11,7 @@ from collections import OrderedDict
 from torch import nn
 
 from ..engine import ConvBN, ConvBNGroup, Gate, Plan, Pool
+from .feature import FeatureMixin
 
 
 class BasicConv3d(nn.Module):
@@ -45,7 +46,7 @@ _POOLS = {"maxPool1": ((1, 3, 3), (1, 2, 2), (0, 1, 1)), "maxPool2": ((1, 3, 3),
           "maxPool3": ((3, 3, 3), (2, 2, 2), (1, 1, 1)), "maxpool4": ((2, 2, 2), (2, 2, 2), (0, 0, 0))}
 
 
-class S3D_G(nn.Module):
+class S3D_G(FeatureMixin, nn.Module):
     classifier_names = ("fc",)
 
     def __init__(self, num_classes=400, drop_prob=0.5, in_channel=3, gate=True):

@@ -665,6 +665,38 @@ class HipOps:
                    "rsp_logits_bwd")
         return dqA, dqM
 
+    # ---- retrieval search (retrieval.hip) ------------------------------------------------------------------------
+    def cosine_topk(self, q, g, k: int, splits: int = 0):
+        """The k nearest rows of g (Ng, D) for every row of q (Nq, D) by cosine distance: (idx int32 (Nq, k), dist fp32 (Nq, k)),
+        best first; ties go to the lower gallery index; idx -1 / dist +inf past Ng.  Rows may be strided (unit column stride,
+        even row pitch).  splits: gallery split count (0: automatic); the result does not depend on it."""
+        for n, t in (("q", q), ("g", g)):
+            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+                raise _lib.RspError(f"cosine_topk: {n} must be a float32 HIP device matrix with unit column stride")
+        Nq, D = q.shape
+        Ng = g.shape[0]
+        if g.shape[1] != D:
+            raise _lib.RspError(f"cosine_topk: feature dims differ ({D} vs {g.shape[1]})")
+        idx = torch.empty((Nq, k), dtype=torch.int32, device=q.device)
+        dist = torch.empty((Nq, k), dtype=torch.float32, device=q.device)
+        wsb = self.lib.rsp_cosine_topk_workspace(Nq, Ng, D, k, int(splits))
+        ws = self._workspace(q.device, wsb)
+        _lib.check(self.lib.rsp_cosine_topk(_ptr(q), q.stride(0) if Nq > 1 else D, Nq, _ptr(g), g.stride(0) if Ng > 1 else D, Ng, D,
+                                            int(k), int(splits), _ptr(idx), _ptr(dist), _ptr(ws), wsb, _stream()),
+                   "rsp_cosine_topk")
+        return idx, dist
+
+    def topk_hits(self, idx, y_q, y_g, ks):
+        """counts[i] = queries whose label is among the labels of their first ks[i] neighbours (int32 device vector)."""
+        _chk(idx, "idx", torch.int32)
+        _chk(y_q, "y_q", torch.int64)
+        _chk(y_g, "y_g", torch.int64)
+        ks_host = (C.c_int32 * len(ks))(*[int(x) for x in ks])
+        counts = torch.empty(len(ks), dtype=torch.int32, device=idx.device)
+        _lib.check(self.lib.rsp_topk_hits(_ptr(idx), idx.shape[0], idx.shape[1], _ptr(y_q), _ptr(y_g), y_g.shape[0], ks_host,
+                                          len(ks), _ptr(counts), _stream()), "rsp_topk_hits")
+        return counts
+
     def loss_fwd_bwd(self, l1, l2, lp, ln, margin: float, A: float, M: float):
         B, K1 = l1.shape
         dev = l1.device
