@@ -441,6 +441,34 @@ int rsp_cosine_topk(const float* q, int32_t ldq, int32_t Nq, const float* g, int
 int rsp_topk_hits(const int32_t* idx, int32_t Nq, int32_t k, const int64_t* y_q, const int64_t* y_g, int32_t Ng,
                   const int32_t* ks_host, int32_t nks, int32_t* counts, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Everything behind the classifier's logits in the fine-tune loop (classify.hip; the reference's finetune.py:101-143), one call:
+ * EpochContext.average_logits (:54-61), nn.CrossEntropyLoss forward + gradient (:105, Engine.criterion :187), the tail cut
+ * (:112-119), accuracy(output, target, topk=(1, 5)) (:132-139, framework/metrics/classification.py:6-20) and the three
+ * AverageMeter.update calls (:135-141, framework/meters/average.py:22-26).
+ * logits: rows x classes fp32, row pitch ld >= classes, the n_crop (1..32) crops of a sample adjacent; S = rows / n_crop samples
+ * (rows % n_crop != 0: RSP_EINVAL); classes 1..4096; target: S int64 labels; 0 <= valid <= S.
+ *   avg_logits [S][classes]  fp32 sum of a sample's crop rows in crop order, divided by n_crop (a copy when n_crop = 1).
+ *   loss [1]                 mean over ALL S samples of logsumexp(avg[s]) - avg[s][target[s]] (row max subtracted first).
+ *   dlogits [rows][classes]  (softmax(avg[s])[c] - [c == target[s]]) / (S * n_crop) in every crop row of sample s; may be NULL.
+ *   acc [2]                  top-1 / top-5 hit rate in percent over the first `valid` samples: fp32(hits) * fp32(100.0 / valid).
+ *                            rank(s) = #{c : avg[s][c] > avg[s][t]} + #{c < t : avg[s][c] == avg[s][t]}, t = target[s]; top-1:
+ *                            rank 0, top-5: rank < 5 -- an exact tie goes to the lower class index (torch.topk leaves it open).
+ *   meters                   device struct, may be NULL: val[i] = v_i, sum[i] += v_i * valid, count[i] += valid for (loss, acc1, acc5).
+ * classes < 5: acc[1] and the acc5 meter are left untouched (:137-139).  valid == 0: only avg_logits, loss and dlogits are written
+ * (:121-122).  A target outside [0, classes) or a NaN logit makes that sample's loss (and so `loss`) NaN and the sample a miss; the
+ * gradient rows of a sample with a bad target are NaN.  No atomics: the same input gives the same bits.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct rsp_cls_meters {   /* order: loss, acc1, acc5 */
+  float val[3];
+  float sum[3];
+  int32_t count[3];
+} rsp_cls_meters;
+size_t rsp_xent_metrics_workspace(int32_t rows, int32_t n_crop);
+int rsp_xent_metrics(const float* logits, int32_t rows, int32_t classes, int32_t ld, int32_t n_crop, const int64_t* target,
+                     int32_t valid, float* avg_logits, float* dlogits, float* loss, float* acc, rsp_cls_meters* meters,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,11 @@ class AugmentClipDesc(C.Structure):
                 ("factor", C.c_float * 4), ("one_minus", C.c_float * 4)]
 
 
+class ClsMeters(C.Structure):
+    """rsp_cls_meters (36 bytes): loss, acc1, acc5"""
+    _fields_ = [("val", C.c_float * 3), ("sum", C.c_float * 3), ("count", C.c_int32 * 3)]
+
+
 _PD = C.POINTER(ConvDesc)
 _PP = C.POINTER(PoolDesc)
 _sz = C.c_size_t
@@ -143,6 +148,8 @@ SIGNATURES = {
     "rsp_cosine_topk_workspace": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "rsp_cosine_topk": (C.c_int, [_p, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _sz, _p]),
     "rsp_topk_hits": (C.c_int, [_p, _i32, _i32, _p, _p, _i32, C.POINTER(C.c_int32), _i32, _p, _p]),
+    "rsp_xent_metrics_workspace": (_sz, [_i32, _i32]),
+    "rsp_xent_metrics": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -80,7 +80,9 @@ class ModelFactory:
         model_cfg = dict(self._get("model"))
         model = MultiTaskWrapper(get_model_class(**model_cfg), num_classes=int(self._get("dataset.num_classes")), finetune=True)
         model = self._post_process_model(model)
-        model = model.to(torch.device("cuda", local_rank))
+        # (finetune.py:160-161: cuda:local_rank, the CPU only where there is no GPU -- there the model runs on the checker
+        #  backend the CPU tests install and on nothing else: HipOps refuses host tensors)
+        model = model.to(torch.device("cuda", local_rank) if torch.cuda.is_available() else torch.device("cpu"))
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             return nn.parallel.DistributedDataParallel(model, device_ids=[local_rank], find_unused_parameters=True)
         return _SingleProcess(model)

@@ -697,6 +697,36 @@ class HipOps:
                                           len(ks), _ptr(counts), _stream()), "rsp_topk_hits")
         return counts
 
+    # ---- fine-tune criterion, accuracy and meters (classify.hip) -------------------------------------------------
+    def xent_metrics(self, logits, target, n_crop: int = 1, valid: Optional[int] = None, want_grad: bool = True, meters=None):
+        """Crop mean, cross-entropy (loss and, with want_grad, its gradient with respect to the crop logits), top-1 / top-5
+        accuracy over the first `valid` samples and the meter update, in one call (rsp_xent_metrics).  logits: (S * n_crop,
+        classes) fp32 with unit column stride; target: (S,) int64; meters: the 36-byte device struct (uint8 tensor) or None.
+        Returns (avg_logits (S, classes), loss (1,), acc (2,): acc1 / acc5 in percent, dlogits | None).  Ties go to the lower
+        class index.  With fewer than 5 classes acc[1] is not written (undefined here), with valid = 0 neither element is."""
+        if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+            raise _lib.RspError("xent_metrics: logits must be a float32 HIP device matrix with unit column stride")
+        _chk(target, "target", torch.int64)
+        rows, classes = logits.shape
+        if n_crop < 1 or rows % n_crop or target.numel() != rows // n_crop:
+            raise _lib.RspError(f"xent_metrics: {rows} rows, n_crop {n_crop}, {target.numel()} targets do not fit")
+        S = rows // n_crop
+        if meters is not None:
+            _chk(meters, "meters", torch.uint8)
+            if meters.numel() < C.sizeof(_lib.ClsMeters):
+                raise _lib.RspError("xent_metrics: meters must hold one rsp_cls_meters")
+        dev = logits.device
+        avg = torch.empty((S, classes), dtype=torch.float32, device=dev)
+        dlogits = torch.empty((rows, classes), dtype=torch.float32, device=dev) if want_grad else None
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        wsb = int(self.lib.rsp_xent_metrics_workspace(rows, n_crop))
+        ws = self._workspace(dev, wsb)
+        _lib.check(self.lib.rsp_xent_metrics(_ptr(logits), rows, classes, logits.stride(0) if rows > 1 else classes, int(n_crop),
+                                             _ptr(target), S if valid is None else int(valid), _ptr(avg), _ptr(dlogits),
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 4), _ptr(meters), _ptr(ws),
+                                             wsb, _stream()), "rsp_xent_metrics")
+        return avg, out[:1], out[1:], dlogits
+
     def loss_fwd_bwd(self, l1, l2, lp, ln, margin: float, A: float, M: float):
         B, K1 = l1.shape
         dev = l1.device
