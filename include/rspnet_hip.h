@@ -469,6 +469,38 @@ int rsp_xent_metrics(const float* logits, int32_t rows, int32_t classes, int32_t
                      int32_t valid, float* avg_logits, float* dlogits, float* loss, float* acc, rsp_cls_meters* meters,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Similarity maps of the pretext model and their picture panels (cam.hip): MoCoDiffLossTwoFc.cam_visualize
+ * (moco/builder_diffspeed_diffloss.py:449-490) and what visualization.py:52-111 draws from its result.
+ *
+ * cam maps: all four maps from the two NDHWC feature maps, no layout change.
+ *   feat_q, feat_k [B][P][C] fp32, row pitch ld_q / ld_k >= C floats (P = T' * H' * W');
+ *   k_row [B] int32: the row of feat_k that pairs with sample b (identity: the reference's pairing of the shuffled key batch;
+ *     the inverse shuffle: key maps in the caller's order).  A value outside [0, B) makes sample b's four maps NaN;
+ *   w_qA, w_kA [dim_A][C], w_qM, w_kM [dim_M][C]: the head weights (fc1[2].weight, fc2[2].weight) of the two encoders;
+ *   out [4][B][P], order qA, qM, kA, kM.  With X = mean over P of F and kr = k_row[b]:
+ *     out[qA][b][p] = sum_c ((w_kA @ k_X[kr]) @ w_qA)[c] * feat_q[b][p][c]        qM: the same with w_kM, w_qM
+ *     out[kA][b][p] = sum_c ((w_qA @ q_X[b]) @ w_kA)[c] * feat_k[kr][p][c]        kM: the same with w_qM, w_kM
+ *   Each feature map is read twice (pooled mean; dot products).  fp32 accumulation in a fixed order, no atomics: the same input gives
+ *   the same bits.  C + max(dim_A, dim_M) <= 12288 and 2 * C <= 12288 (LDS).  16-byte loads when C, ld_q, ld_k are multiples of 4 and
+ *   the pointers 16-byte aligned; any C otherwise.
+ * the workspace holds [2][B][C] pooled means + [4][B][C] channel vectors.
+ *
+ * cam overlay: N picture panels in one launch.  maps [N][T'][H'][W'] fp32; per panel: mean over T', v = (m - min) / (max - min) over
+ *   (H', W') (max == min: v = 0), bilinear resize of v to size x size with half-pixel centres (align_corners = False, no
+ *   antialiasing), colour r = clamp(1.5 - |4v - 3|), g = clamp(1.5 - |4v - 2|), b = clamp(1.5 - |4v - 1|) clamped to [0, 1],
+ *   pixel = round_to_nearest(0.6 * 255 * frame + 0.4 * 255 * colour) clamped to [0, 255].
+ *   clip_a, clip_b: (B, 3, T, size, size) fp32 clips in [0, 1] (NOT normalised); frame t of sample n % B is drawn under panel n, from
+ *   clip_a for the first N / 2 panels and clip_b for the rest (clip_b NULL: clip_a for all).  H' * W' <= 4096.
+ *   out [N][size][size][3] uint8 RGB.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t rsp_cam_maps_workspace(int32_t B, int32_t C);
+int rsp_cam_maps(const float* feat_q, int32_t ld_q, const float* feat_k, int32_t ld_k, const int32_t* k_row, int32_t B, int32_t P,
+                 int32_t C, const float* w_qA, const float* w_qM, const float* w_kA, const float* w_kM, int32_t dim_A, int32_t dim_M,
+                 float* out, void* workspace, size_t workspace_bytes, void* stream);
+int rsp_cam_overlay(const float* maps, int32_t N, int32_t Tp, int32_t Hp, int32_t Wp, const float* clip_a, const float* clip_b,
+                    int32_t B, int32_t T, int32_t t, int32_t size, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,9 @@ SIGNATURES = {
     "rsp_topk_hits": (C.c_int, [_p, _i32, _i32, _p, _p, _i32, C.POINTER(C.c_int32), _i32, _p, _p]),
     "rsp_xent_metrics_workspace": (_sz, [_i32, _i32]),
     "rsp_xent_metrics": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "rsp_cam_maps_workspace": (_sz, [_i32, _i32]),
+    "rsp_cam_maps": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _sz, _p]),
+    "rsp_cam_overlay": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -352,15 +352,16 @@ class MoCoDiffLossTwoFc(nn.Module):
             log.warning("rspnet_amd: gloo side group unavailable on at least one rank (%s); shuffle permutations are broadcast "
                         "through the device group: one small device sync per step", err)
 
-    def _draw_step_randomness(self, B: int):
+    def _draw_step_randomness(self, B: int, share: bool = True):
         """This step's (speed, idx_shuffle #1, idx_shuffle #2).  Drawn on every rank in the reference's call order
         (random.choice :430, torch.randperm :372 twice); rank 0's values win (:375-378 broadcasts idx_shuffle; the speed must be
         rank-shared as well, or T_real — hence every all-to-all / all-gather shape — would differ across ranks when
-        diff_speed has several entries).  One host-side broadcast carries all three."""
+        diff_speed has several entries).  One host-side broadcast carries all three.  share=False: this rank's own draws, no
+        collective (`cam_visualize(align_keys=True)`, which exchanges nothing)."""
         rank, ws, coll = self._dp()
         speed = random.choice(self.diff_speed)
         sh1, sh2 = torch.randperm(B * ws), torch.randperm(B * ws)
-        if coll:
+        if coll and share:
             msg = torch.cat([torch.tensor([speed], dtype=torch.int64), sh1.to(torch.int64), sh2.to(torch.int64)])
             group = self._cpu_pg()
             if group is not None:
@@ -538,6 +539,61 @@ class MoCoDiffLossTwoFc(nn.Module):
         ptr = (ptr + n) % self.K
         self._ptr_host = ptr
         self.queue_ptr.fill_(ptr)
+
+    # ---- similarity maps ------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def cam_visualize(self, im_q: Tensor, im_k: Tensor, align_keys: bool = False):
+        """:449-490 — the class-activation-style similarity maps of the two heads.  im_q, im_k: (B, 3, T, H, W) fp32.  Returns
+        (Ms_qA, Ms_qM, Ms_kA, Ms_kM), each (B, T', H', W') fp32 with (T', H', W') the backbone's last feature map: with X the pooled
+        feature and w?A / w?M the head weights of encoder ?,
+            Ms_qA[b] = sum_c ((k_wA @ k_X[b]) @ q_wA)[c] * q_F[b, c]        Ms_kA[b] = sum_c ((q_wA @ q_X[b]) @ k_wA)[c] * k_F[b, c]
+        and the same with the M weights (one HIP call, rsp_cam_maps, on the NDHWC features).
+
+        Eval mode only (visualization.py:113-115 calls model.eval() first): BatchNorm runs on its running statistics and the call
+        leaves the model as it found it — no momentum update, no queue, running-statistics or counter movement.  It draws what
+        the reference draws, in its order (:458-461: device randperm(B), random.choice(diff_speed), two shuffle permutations); the
+        k_negative key pass of `_diff_speed` has no effect in eval mode and is not run.
+
+        align_keys=False is the reference's pairing: k_F is the feature of the SHUFFLED key batch (:462), so row b of the key maps
+        belongs to key clip idx_shuffle[b], and Ms_q?[b] uses that clip's pooled feature (one rank only).  align_keys=True: row b
+        belongs to clip b on both sides; eval-mode BatchNorm does not see the batch, so the shuffle is skipped (any world size, no
+        collective).  Afterwards encoder_?._get_last_feature() is the NDHWC feature map the call used."""
+        if self.training:
+            raise NotImplementedError("cam_visualize is defined in eval mode (BatchNorm on its running statistics, as "
+                                      "visualization.py runs it): call model.eval() first")
+        fc_type = self.encoder_q.fc_type
+        if fc_type not in ("linear", "speednet"):
+            raise NotImplementedError(f"cam_visualize reads the heads' single Linear weight (fcN[2], _get_fc_weight): fc_type "
+                                      f"'{fc_type}' has none (the reference fails there too); use 'linear' or 'speednet'")
+        _, ws, _ = self._dp()
+        if ws > 1 and not align_keys:
+            raise NotImplementedError("cam_visualize(align_keys=False) pairs rows of the shuffled key batch across ranks in the "
+                                      "reference; with more than one rank use align_keys=True")
+        be = _ops.backend()
+        dev = im_q.device
+        B, C, T, H, W = im_q.shape
+        im_q, im_k = im_q.contiguous(), im_k.contiguous()
+        if not self._q_params:
+            self._q_params = list(self.encoder_q.parameters())
+        self._check_q_weights()
+        # _diff_speed (:421-447) and the two _forward_encoder_k draws (:372), in the reference's order
+        random_indices = torch.randperm(B, device=dev)
+        speed, _, sh2 = self._draw_step_randomness(B, share=False)
+        T_real = T // speed
+        step_q = torch.full((B,), speed, dtype=torch.int32, device=dev)
+        step_q.index_fill_(0, random_indices[:int(B * self.alpha)], 1)
+        src = torch.arange(B, dtype=torch.int32, device=dev)
+        src_k = src if align_keys else self._upload_indices([sh2.astype(np.int32)], dev)[0]
+        x_k, x_q = be.clip_gather_multi([(im_k, src_k, step_q[src_k.long()].contiguous()), (im_q, src, step_q)], T_real,
+                                        max(C, INPUT_CHANNEL_PAD))
+        self.encoder_k.forward_ndhwc(x_k, keep=False, training=False)
+        self.encoder_q.forward_ndhwc(x_q, keep=False, training=False)
+        q_F, k_F = self.encoder_q._get_last_feature(), self.encoder_k._get_last_feature()
+        q_wA, q_wM = self.encoder_q._get_fc_weight()
+        k_wA, k_wM = self.encoder_k._get_fc_weight()
+        # row b of k_F pairs with sample b in both modes (the shuffled batch IS the reference's pairing; aligned keys were never shuffled)
+        maps = be.cam_maps(q_F, k_F, src, q_wA.contiguous(), q_wM.contiguous(), k_wA.contiguous(), k_wM.contiguous())
+        return maps[0], maps[1], maps[2], maps[3]
 
     # ---- backward of the query encoder -------------------------------------------------------------------------------
     def _backward_encoder_q(self, ectx, dqA, dqM):

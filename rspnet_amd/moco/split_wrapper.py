@@ -140,11 +140,15 @@ class MultiTaskWrapper(nn.Module):
     def weights_changed(self):
         self._packed.invalidate()
 
-    def forward_ndhwc(self, x: Tensor, keep: bool, deferred=None):
+    def forward_ndhwc(self, x: Tensor, keep: bool, deferred=None, training: bool = True):
         """x: (N,T,H,W,C).  Returns (x1, x2, ctx) — ctx is what backward_ndhwc needs (None when keep=False).  deferred: see
-        engine.run_forward (BatchNorm layers that report their batch moments instead of moving their running statistics)."""
+        engine.run_forward (BatchNorm layers that report their batch moments instead of moving their running statistics).
+        training=False: BatchNorm — the backbone's and a 'convbn' head's — on its running statistics (model.eval(): the
+        similarity maps of MoCoDiffLossTwoFc.cam_visualize); nothing is kept for a backward then."""
+        if keep and not training:
+            raise ValueError("forward_ndhwc: an eval-mode forward (training=False) keeps nothing for a backward (keep=True)")
         be = _ops.backend()
-        feat, ctx = run_forward(self.plan(), x, self._packed, keep, deferred=deferred)
+        feat, ctx = run_forward(self.plan(), x, self._packed, keep, training=training, deferred=deferred)
         self.feat = feat
         if self.fc_type == "linear":
             l1, l2 = self.fc1[2], self.fc2[2]
@@ -158,7 +162,7 @@ class MultiTaskWrapper(nn.Module):
         for hi, fc in enumerate((self.fc1, self.fc2)):
             hctx = hid = None
             if self.fc_type in ("conv", "convbn"):
-                h, hctx = run_forward(fc.plan(), feat, self._packed, keep, deferred=deferred)
+                h, hctx = run_forward(fc.plan(), feat, self._packed, keep, training=training, deferred=deferred)
                 pooled = be.spatial_mean_fwd(h)
                 raw = be.linear_fwd(pooled, fc.linear.weight.data, fc.linear.bias.data, False)
                 hshape = tuple(h.shape)

@@ -727,6 +727,51 @@ class HipOps:
                                              wsb, _stream()), "rsp_xent_metrics")
         return avg, out[:1], out[1:], dlogits
 
+    # ---- similarity maps and their picture panels (cam.hip) --------------------------------------------------------
+    def cam_maps(self, feat_q, feat_k, k_row, w_qA, w_qM, w_kA, w_kM):
+        """The four similarity maps of MoCoDiffLossTwoFc.cam_visualize from the two NDHWC feature maps (B, T', H', W', C) — dense, or
+        channel slices of a wider tensor — in one call (rsp_cam_maps).  k_row: (B,) int32, the row of feat_k that pairs with sample b.
+        Returns (4, B, T', H', W') fp32, order qA, qM, kA, kM."""
+        ld_q, ld_k = _rows_ld(feat_q, "feat_q"), _rows_ld(feat_k, "feat_k")
+        if feat_q.dim() != 5 or feat_q.shape != feat_k.shape:
+            raise _lib.RspError(f"cam_maps: feature maps must be two (B, T', H', W', C) tensors of one shape, got "
+                                f"{tuple(feat_q.shape)} and {tuple(feat_k.shape)}")
+        B, D, H, W, Cc = feat_q.shape
+        P = D * H * W
+        _chk(k_row, "k_row", torch.int32)
+        if k_row.numel() != B:
+            raise _lib.RspError(f"cam_maps: k_row must hold {B} rows, not {k_row.numel()}")
+        for n, w, like in (("w_qA", w_qA, w_kA), ("w_qM", w_qM, w_kM), ("w_kA", w_kA, w_qA), ("w_kM", w_kM, w_qM)):
+            _chk(w, n)
+            if w.dim() != 2 or w.shape[1] != Cc or w.shape != like.shape:
+                raise _lib.RspError(f"cam_maps: {n} must be (dim, {Cc}) and match the other encoder's, got {tuple(w.shape)}")
+        dev = feat_q.device
+        out = torch.empty((4, B, D, H, W), dtype=torch.float32, device=dev)
+        wsb = int(self.lib.rsp_cam_maps_workspace(B, Cc))
+        ws = self._workspace(dev, wsb)
+        _lib.check(self.lib.rsp_cam_maps(_ptr(feat_q), ld_q, _ptr(feat_k), ld_k, _ptr(k_row), B, P, Cc, _ptr(w_qA), _ptr(w_qM),
+                                         _ptr(w_kA), _ptr(w_kM), w_qA.shape[0], w_qM.shape[0], _ptr(out), _ptr(ws), wsb, _stream()),
+                   "rsp_cam_maps")
+        return out
+
+    def cam_overlay(self, maps, clip_a, clip_b, t: int):
+        """N picture panels (N, size, size, 3) uint8 RGB in one launch (rsp_cam_overlay): maps (N, T', H', W') fp32; frame `t` of
+        sample n % B of the un-normalised [0, 1] clip (B, 3, T, size, size) under panel n — clip_a for the first half of the panels,
+        clip_b for the second (clip_b None: clip_a for all)."""
+        _chk(maps, "maps")
+        _chk(clip_a, "clip_a")
+        if maps.dim() != 4 or clip_a.dim() != 5 or clip_a.shape[1] != 3 or clip_a.shape[3] != clip_a.shape[4]:
+            raise _lib.RspError(f"cam_overlay: expected maps (N, T', H', W') and clips (B, 3, T, size, size), got {tuple(maps.shape)} "
+                                f"and {tuple(clip_a.shape)}")
+        if clip_b is not None and (_chk(clip_b, "clip_b").shape != clip_a.shape):
+            raise _lib.RspError("cam_overlay: the two clips must have one shape")
+        N, Tp, Hp, Wp = maps.shape
+        B, _, T, size, _ = clip_a.shape
+        out = torch.empty((N, size, size, 3), dtype=torch.uint8, device=maps.device)
+        _lib.check(self.lib.rsp_cam_overlay(_ptr(maps), N, Tp, Hp, Wp, _ptr(clip_a), _ptr(clip_b), B, T, int(t), size, _ptr(out),
+                                            _stream()), "rsp_cam_overlay")
+        return out
+
     def loss_fwd_bwd(self, l1, l2, lp, ln, margin: float, A: float, M: float):
         B, K1 = l1.shape
         dev = l1.device
