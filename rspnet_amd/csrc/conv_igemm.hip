@@ -1887,6 +1887,19 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const rsp_pack_job* __r
   for (int k = j.ntaps * j.C + threadIdx.x; k < j.Kld; k += 256) row[k] = 0.f;
 }
 
+// The kernel families of the convolution launch plan (ConvPlan below) and, one per family, how an instance is spelled: as rocprofv3
+// prints the demangled instance (minus namespace and argument list).  The launchers note what they start with these formats
+// (rsp_note_kernel) and rsp_conv3d_kernel_name formats the plan's first launch with them.
+enum KernelFamily { K_DIRECT, K_TILE, K_TILE_KS, K_PERSIST, K_PERSIST_FOLD, K_MULTI };
+constexpr const char* kernel_format(KernelFamily f) {      // arguments: BM, BN, WAVES_M, WAVES_N, then VEC or "true" / "false" (KS), then MINW or FOLD
+  return f == K_DIRECT ? "igemm_direct_kernel"
+       : f == K_TILE ? "igemm_kernel<%d, %d, %d, %d, %d, %d>"
+       : f == K_TILE_KS ? "igemm_ks_kernel<%d, %d, %d, %d>"
+       : f == K_PERSIST ? "igemm_persist_kernel<%d, %d, %d, %d, %s, %d>"
+       : f == K_PERSIST_FOLD ? "igemm_persist_fold_kernel<%d, %d, %d, %d, %s, %d>"
+                             : "igemm_multi_kernel<%d, %d, %d, %d, %d, %d>";
+}
+
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 int launch_ks_cfg(const IgemmParams& p, hipStream_t s) {
   const size_t lds = (size_t)p.nbuf * (BM + BN) * BK * sizeof(float) + (size_t)(p.nTd * p.nTh * p.nTw + 1) * sizeof(int4) + BM * sizeof(long long);
@@ -1898,7 +1911,7 @@ int launch_ks_cfg(const IgemmParams& p, hipStream_t s) {
     attr_set = true;
   }
   dim3 grid(p.full_tiles + (p.m_tiles * p.n_tiles - p.full_tiles) * p.splitk);
-  rsp_note_kernel("igemm_ks_kernel<%d, %d, %d, %d>", BM, BN, WAVES_M, WAVES_N);
+  rsp_note_kernel(kernel_format(K_TILE_KS), BM, BN, WAVES_M, WAVES_N);
   hipLaunchKernelGGL((igemm_ks_kernel<BM, BN, WAVES_M, WAVES_N>), grid, dim3(256), lds, s, p);
   return rsp_check_launch("igemm_ks_kernel");
 }
@@ -1919,7 +1932,7 @@ int launch_cfg(const IgemmParams& p, hipStream_t s) {
     attr_set = true;
   }
   dim3 grid(p.full_tiles + (p.m_tiles * p.n_tiles - p.full_tiles) * p.splitk);
-  rsp_note_kernel("igemm_kernel<%d, %d, %d, %d, %d, %d>", BM, BN, WAVES_M, WAVES_N, VEC, MINW);
+  rsp_note_kernel(kernel_format(K_TILE), BM, BN, WAVES_M, WAVES_N, VEC, MINW);
   hipLaunchKernelGGL((igemm_kernel<BM, BN, WAVES_M, WAVES_N, VEC, MINW>), grid, dim3(256), lds, s, p);
   return rsp_check_launch("igemm_kernel");
 }
@@ -1969,7 +1982,6 @@ inline int narrow_bn(long long M, int Cout, int nchunks) {
   const bool cols = Cout > 160 || (Cout > 96 && Cout <= 128);
   return (cols && mt * rsp_cdiv(Cout, 128) < narrow_max_tiles()) ? 64 : 0;
 }
-inline int tile_bn_of(const IgemmParams& p) { return p.bn_narrow ? p.bn_narrow : tile_bn(p.Cout); }
 
 // 256 x 64 tiles for 33..64-column launches (round 6): four waves stacked along M, each 64 rows x 64 columns — the
 // wave tile, accumulator count and LDS bytes per MFMA of the 128 x 128 instance (141 TF on C3D), where the 128 x 64 tile's waves
@@ -2003,7 +2015,7 @@ int launch_multi_cfg(const IgemmMulti& m, int max_taps, hipStream_t s) {
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
     attr_set = true;
   }
-  rsp_note_kernel("igemm_multi_kernel<%d, %d, %d, %d, %d, %d>", BM, BN, WAVES_M, WAVES_N, VEC, MINW);
+  rsp_note_kernel(kernel_format(K_MULTI), BM, BN, WAVES_M, WAVES_N, VEC, MINW);
   hipLaunchKernelGGL((igemm_multi_kernel<BM, BN, WAVES_M, WAVES_N, VEC, MINW>), dim3(m.start[m.n]), dim3(256), lds, s, m);
   return rsp_check_launch("igemm_multi_kernel");
 }
@@ -2040,7 +2052,7 @@ int launch_persist_cfg(const IgemmParams& p, hipStream_t s) {
   wpc = wpc > MINW ? MINW : (wpc < 1 ? 1 : wpc);
   int G = 256 * wpc;
   if (n_units <= G) G = n_units;
-  rsp_note_kernel("igemm_persist_kernel<%d, %d, %d, %d, %s, %d>", BM, BN, WAVES_M, WAVES_N, KS ? "true" : "false", MINW);
+  rsp_note_kernel(kernel_format(K_PERSIST), BM, BN, WAVES_M, WAVES_N, KS ? "true" : "false", MINW);
   hipLaunchKernelGGL((igemm_persist_kernel<BM, BN, WAVES_M, WAVES_N, KS, MINW>), dim3(G), dim3(256), lds, s, p, n_units);
   return rsp_check_launch("igemm_persist_kernel");
 }
@@ -2076,7 +2088,7 @@ int launch_persist_fold_cfg(const IgemmParams& p, hipStream_t s) {
   wpc = wpc > 2 ? 2 : (wpc < 1 ? 1 : wpc);
   int G = 256 * wpc;
   if (n_units <= G) G = n_units;
-  rsp_note_kernel("igemm_persist_fold_kernel<%d, %d, %d, %d, %s, %d>", BM, BN, WAVES_M, WAVES_N, KS ? "true" : "false", FOLD);
+  rsp_note_kernel(kernel_format(K_PERSIST_FOLD), BM, BN, WAVES_M, WAVES_N, KS ? "true" : "false", FOLD);
   hipLaunchKernelGGL((igemm_persist_fold_kernel<BM, BN, WAVES_M, WAVES_N, KS, FOLD>), dim3(G), dim3(256), lds, s, p, n_units);
   return rsp_check_launch("igemm_persist_fold_kernel");
 }
@@ -2087,48 +2099,78 @@ static bool half_block_cols(int cols) {
   static const bool off = getenv("RSP_NO_HALF_BLOCK") != nullptr;
   return !off && cols > 128 && cols <= 144;
 }
-static bool half_block(const IgemmParams& p) { return half_block_cols(p.Cout); }
 
-int launch_persist(IgemmParams& p, hipStream_t s) {
-  const int bn = tile_bn_of(p);
-  const int bm = p.bm > 128 ? 256 : 128;
-  p.m_tiles = rsp_cdiv(p.M, bm);
-  p.n_tiles = rsp_cdiv(p.Cout, bn);
-  const int R = p.m_tiles * p.n_tiles - p.full_tiles;
-  p.dR = fastdiv_make(R > 0 ? R : 1);
-  p.dNtl = fastdiv_make(p.n_tiles);
-  if (bm == 256) {      // the tall 64-wide instance (tall_tiles)
-    if (bn != 64) {
-      rsp_set_error("launch_persist: the 256-row tile is 64 columns wide");
-      return RSP_EINVAL;
-    }
-    return p.kmajor ? launch_persist_cfg<256, 64, 4, 1, true>(p, s) : launch_persist_cfg<256, 64, 4, 1, false>(p, s);
-  }
-  if (p.kmajor) {
-    if (bn == 128 && two_level_min_chunks() > 0 && p.nchunks >= two_level_min_chunks())
-      return launch_persist_fold_cfg<128, 128, 2, 2, true, FOLD_CHUNKS>(p, s);
-    switch (bn) {
-      case 160: return half_block(p) ? launch_persist_cfg<128, 144, 4, 1, true>(p, s) : launch_persist_cfg<128, 160, 4, 1, true>(p, s);
-      case 128: return launch_persist_cfg<128, 128, 2, 2, true>(p, s);
-      case 96: return launch_persist_cfg<128, 96, 4, 1, true>(p, s);
-      case 64: return launch_persist_cfg<128, 64, 2, 2, true>(p, s);
-      default: return launch_persist_cfg<128, 32, 4, 1, true>(p, s);
-    }
-  }
-  switch (bn) {
-    case 160: return half_block(p) ? launch_persist_cfg<128, 144, 4, 1, false>(p, s) : launch_persist_cfg<128, 160, 4, 1, false>(p, s);
-    case 128: return launch_persist_cfg<128, 128, 2, 2, false>(p, s);
-    case 96: return launch_persist_cfg<128, 96, 4, 1, false>(p, s);
-    case 64: return launch_persist_cfg<128, 64, 2, 2, false>(p, s);
-    default: return launch_persist_cfg<128, 32, 4, 1, false>(p, s);
-  }
+// ---- the launch plan: decided ONCE per convolution (plan_conv), then executed (run_igemm), named (rsp_conv3d_kernel_name), sized
+// (rsp_conv3d_*_workspace) and priced (rsp_conv3d_executed_fraction) from the same struct ---------------------------------------
+struct LaunchPlan {      // one kernel launch (+ its reduce launch when splitk > 1)
+  KernelFamily family;
+  int bm, bn, waves_m, waves_n;      // template parameters of the instance
+  int vec;                           // VEC of the per-tile and multi kernels (4: LDS-DMA, 1: scalar gather)
+  bool ks;                           // KS of the persistent kernels (the slice-major K walk)
+  int minw;                          // MINW; FOLD of the two-level instance
+  int c0, cols, bn_narrow;           // the column segment; 64 / 32: that tile width over all columns (narrow_bn)
+  int nbuf, full_tiles, splitk, chunks_per_split, tail_row0;      // as in IgemmParams
+  size_t partial_bytes;              // workspace of the K split (every launch of a plan starts at the workspace's base)
+};
+struct ConvPlan {
+  int n;      // launches: one, or two column segments
+  LaunchPlan l[2];
+};
+
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+int launch_persist_ks(const IgemmParams& p, bool ks, hipStream_t s) {
+  return ks ? launch_persist_cfg<BM, BN, WAVES_M, WAVES_N, true>(p, s) : launch_persist_cfg<BM, BN, WAVES_M, WAVES_N, false>(p, s);
+}
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+int launch_cfg_vec(const IgemmParams& p, int vec, hipStream_t s) {
+  return vec == 4 ? launch_cfg<BM, BN, WAVES_M, WAVES_N, 4>(p, s) : launch_cfg<BM, BN, WAVES_M, WAVES_N, 1>(p, s);
 }
 
-// bytes reachable from the output base pointer (all positions of the output tensor, this segment's columns); 0 if >= 4 GiB
-static unsigned out_extent_bytes(const IgemmParams& p) {
-  const unsigned long long pos = (unsigned long long)p.Nb * p.oDm * p.oHm * p.oWm;
-  const unsigned long long b = ((pos - 1) * (unsigned long long)p.out_ld + (unsigned long long)p.Cout) * 4ull;
-  return b < 0x7ffffff0ull ? (unsigned)b : 0u;      // (< 2 GiB: an offset with bit 31 set is out of range whatever is added to it)
+// The runtime tile shape of a planned launch becomes a template instance here, once per kernel family.
+int launch_planned(IgemmParams& p, const LaunchPlan& l, hipStream_t s) {
+  p.m_tiles = rsp_cdiv(p.M, l.bm);
+  p.n_tiles = rsp_cdiv(p.Cout, l.bn);
+  const int key = l.bm * 1000 + l.bn;
+  switch (l.family) {
+    case K_PERSIST:
+    case K_PERSIST_FOLD: {
+      const int R = p.m_tiles * p.n_tiles - p.full_tiles;
+      p.dR = fastdiv_make(R > 0 ? R : 1);
+      p.dNtl = fastdiv_make(p.n_tiles);
+      if (l.family == K_PERSIST_FOLD) return launch_persist_fold_cfg<128, 128, 2, 2, true, FOLD_CHUNKS>(p, s);
+      switch (key) {
+        case 256064: return launch_persist_ks<256, 64, 4, 1>(p, l.ks, s);      // the tall 64-wide instance (tall_tiles)
+        case 128160: return launch_persist_ks<128, 160, 4, 1>(p, l.ks, s);
+        case 128144: return launch_persist_ks<128, 144, 4, 1>(p, l.ks, s);
+        case 128128: return launch_persist_ks<128, 128, 2, 2>(p, l.ks, s);
+        case 128096: return launch_persist_ks<128, 96, 4, 1>(p, l.ks, s);
+        case 128064: return launch_persist_ks<128, 64, 2, 2>(p, l.ks, s);
+        case 128032: return launch_persist_ks<128, 32, 4, 1>(p, l.ks, s);
+      }
+      break;
+    }
+    case K_TILE_KS:
+      switch (key) {
+        case 128160: return launch_ks_cfg<128, 160, 4, 1>(p, s);
+        case 128128: return launch_ks_cfg<128, 128, 2, 2>(p, s);
+        case 128096: return launch_ks_cfg<128, 96, 4, 1>(p, s);
+        case 128064: return launch_ks_cfg<128, 64, 2, 2>(p, s);
+        case 128032: return launch_ks_cfg<128, 32, 4, 1>(p, s);
+      }
+      break;
+    case K_TILE:
+      switch (l.vec == 4 ? key : -key) {      // (the scalar-gather fallback only has the power-of-two tiles)
+        case 128160: return launch_cfg<128, 160, 4, 1, 4>(p, s);
+        case 128096: return launch_cfg<128, 96, 4, 1, 4>(p, s);
+        case 128128: case -128128: return launch_cfg_vec<128, 128, 2, 2>(p, l.vec, s);
+        case 128064: case -128064: return launch_cfg_vec<128, 64, 2, 2>(p, l.vec, s);
+        case 128032: case -128032: return launch_cfg_vec<128, 32, 4, 1>(p, l.vec, s);
+      }
+      break;
+    default: break;
+  }
+  rsp_set_error("launch_planned: no such kernel instance");
+  return RSP_EINVAL;
 }
 
 inline void fill_fastdiv_linear(IgemmParams& p) {
@@ -2171,28 +2213,6 @@ inline void fill_fastdiv(IgemmParams& p) {
   (void)ntaps;
   p.dNt = fastdiv_make(p.nTd * p.nTh * p.nTw);
   fill_fastdiv_linear(p);
-}
-
-int launch_igemm(IgemmParams& p, bool vec4, hipStream_t s) {
-  // BM is fixed at 128 (stat partials are defined on 128-row tiles); BN follows Cout.
-  int bn = tile_bn_of(p);
-  if (!vec4 && (bn == 160 || bn == 96)) bn = 128;      // the scalar-gather fallback only has the power-of-two tiles
-  p.m_tiles = rsp_cdiv(p.M, 128);
-  p.n_tiles = rsp_cdiv(p.Cout, bn);
-  if (vec4 && p.kmajor) {
-    switch (bn) {
-      case 160: return launch_ks_cfg<128, 160, 4, 1>(p, s);
-      case 128: return launch_ks_cfg<128, 128, 2, 2>(p, s);
-      case 96: return launch_ks_cfg<128, 96, 4, 1>(p, s);
-      case 64: return launch_ks_cfg<128, 64, 2, 2>(p, s);
-      default: return launch_ks_cfg<128, 32, 4, 1>(p, s);
-    }
-  }
-  if (bn == 160) return launch_cfg<128, 160, 4, 1, 4>(p, s);
-  if (bn == 96) return launch_cfg<128, 96, 4, 1, 4>(p, s);
-  if (bn == 128) return vec4 ? launch_cfg<128, 128, 2, 2, 4>(p, s) : launch_cfg<128, 128, 2, 2, 1>(p, s);
-  if (bn == 64) return vec4 ? launch_cfg<128, 64, 2, 2, 4>(p, s) : launch_cfg<128, 64, 2, 2, 1>(p, s);
-  return vec4 ? launch_cfg<128, 32, 4, 1, 4>(p, s) : launch_cfg<128, 32, 4, 1, 1>(p, s);
 }
 
 // Tail split by a small cost model.  A CU holds `wpc` workgroups of this tile shape, so the machine has 256*wpc slots and
@@ -2256,20 +2276,8 @@ SplitPlan plan_split(int m_tiles, int n_tiles, int bn, bool vec4, int nchunks, i
   return best;
 }
 
-bool desc_ok(const rsp_conv3d_desc* d) {
-  if (!d) return false;
-  if (d->N <= 0 || d->Cin <= 0 || d->Cout <= 0) return false;
-  if (d->kT * d->kH * d->kW > MAX_TAPS || d->kT <= 0 || d->kH <= 0 || d->kW <= 0) return false;
-  if (d->sT <= 0 || d->sH <= 0 || d->sW <= 0 || d->pT < 0 || d->pH < 0 || d->pW < 0) return false;
-  if (d->Do != (d->Di + 2 * d->pT - d->kT) / d->sT + 1) return false;
-  if (d->Ho != (d->Hi + 2 * d->pH - d->kH) / d->sH + 1) return false;
-  if (d->Wo != (d->Wi + 2 * d->pW - d->kW) / d->sW + 1) return false;
-  if (d->Do <= 0 || d->Ho <= 0 || d->Wo <= 0) return false;
-  if (d->in_ld < d->Cin || d->out_ld < d->Cout) return false;
-  if ((long long)d->N * d->Do * d->Ho * d->Wo >= (1ll << 31)) return false;
-  if ((long long)d->N * d->Di * d->Hi * d->Wi >= (1ll << 31)) return false;
-  return true;
-}
+// (forward and input gradient also index the input positions with 31 bits)
+bool desc_ok(const rsp_conv3d_desc* d) { return rsp_conv_desc_ok(d) && (long long)d->N * d->Di * d->Hi * d->Wi < (1ll << 31); }
 
 void fill_reduce(ReduceParams& r, const IgemmParams& p) {
   r.partial = p.partial;
@@ -2296,61 +2304,6 @@ size_t split_partial_bytes(const SplitPlan& sp, long long M, int n_tiles, int Co
   if (sp.splitk <= 1) return 0;
   const long long row0 = (long long)(sp.full_tiles / n_tiles) * bm;
   return (size_t)sp.splitk * (size_t)(M - row0) * Cout * sizeof(float);
-}
-
-int run_igemm_segment(IgemmParams& p, bool vec4, void* workspace, size_t ws_bytes, hipStream_t s) {
-  const float* zero_page = igemm_zero_page();
-  if (!zero_page) {
-    rsp_set_error("hipGetSymbolAddress(g_zero) failed");
-    return RSP_ELAUNCH;
-  }
-  p.zero = zero_page;
-  p.nchunks = rsp_cdiv(p.K, BK);
-  fill_fastdiv(p);
-  if (!vec4) {      // only the LDS-DMA kernels know the depth-major enumeration and the skipping walks
-    p.dmajor = 0;
-    p.tm_skip = 0;
-    fill_fastdiv_linear(p);
-  }
-  int bn = tile_bn_of(p);
-  if (!vec4 && (bn == 160 || bn == 96)) bn = 128;
-  p.y_bytes = out_extent_bytes(p);
-  // rows per tile: 256 on the tall 64-wide instance of the persistent kernel (tall_tiles), which needs 32-bit output offsets
-  const int bm = (tall_tiles(p.M, bn, vec4) && persist_enabled() && p.y_bytes != 0) ? 256 : 128;
-  p.bm = bm;
-  const int m_tiles = rsp_cdiv(p.M, bm), n_tiles = rsp_cdiv(p.Cout, bn);
-  SplitPlan sp = plan_split(m_tiles, n_tiles, bn, vec4, p.nchunks, p.Cout, bm);
-  p.nbuf = (bm == 256 || single_buffer(m_tiles, n_tiles, bn, vec4)) ? 1 : 2;
-  if (sp.splitk > 1 && (!workspace || ws_bytes < split_partial_bytes(sp, p.M, n_tiles, p.Cout, bm)))
-    sp = {m_tiles * n_tiles, 1, p.nchunks};   // degrade gracefully: still correct
-  p.full_tiles = sp.full_tiles;
-  p.splitk = sp.splitk;
-  p.chunks_per_split = sp.cps;
-  p.tail_row0 = sp.full_tiles / n_tiles * bm;
-  p.partial = p.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
-  const size_t pbytes = split_partial_bytes(sp, p.M, n_tiles, p.Cout, bm);
-  p.partial_bytes = pbytes < 0x7ffffff0ull ? (unsigned)pbytes : 0u;
-  // (the long tap-major 128-wide launches — C3D conv2: 54 chunks per tile — measured 1 % faster on the per-tile kernel; everything
-  //  else equal or better persistent: R3D-18 +2.9 %, R(2+1)D / S3D-G +0.3 % per step, profiles/r04/experiments_r4.txt)
-  const bool long_tm128 = !p.kmajor && bn == 128 && p.nchunks >= 48;
-  const bool persist = vec4 && persist_enabled() && !long_tm128 && p.y_bytes != 0 && (p.splitk == 1 || p.partial_bytes != 0);
-  // the persistent 64-wide tile is compiled for four waves per SIMD (121-128 VGPRs): with ONE tile buffer (24.5 KB) four workgroups
-  // share a CU on launches of at least one such round (R3D-18 +0.5 %, R(2+1)D +0.2 % per step); the per-tile 64-wide kernel, three
-  // per CU either way, lost 9 % to the extra barrier (single_buffer)
-  if (persist && bm == 128 && bn == 64 && (long long)m_tiles * n_tiles >= 1024) p.nbuf = 1;
-  int rc = persist ? launch_persist(p, s) : launch_igemm(p, vec4, s);
-  if (rc != RSP_OK) return rc;
-  if (p.splitk > 1) {
-    ReduceParams r;
-    fill_reduce(r, p);
-    dim3 grid(rsp_cdiv(p.M - p.tail_row0, 128), rsp_cdiv(p.Cout, 64));
-    if (p.Cout % 4 == 0 && p.out_ld % 4 == 0 && rsp_aligned16(p.y) && (!p.bias || rsp_aligned16(p.bias)))
-      hipLaunchKernelGGL(splitk_reduce_vec_kernel, grid, dim3(256), 0, s, r);
-    else
-      hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, s, r);
-    rc = rsp_check_launch("splitk_reduce_kernel");
-  }
-  return rc;
 }
 
 // Column segments of one GEMM.  The N tiles are 128 wide (64 / 32 for narrow outputs); a channel count such as 144, 160 or 288
@@ -2437,91 +2390,173 @@ static bool multi_split_enabled() {
   static const bool off = getenv("RSP_NO_MULTI_SPLIT") != nullptr;      // (A/B switch for measurements, read once)
   return !off;
 }
-int run_direct(IgemmParams& p, void* workspace, size_t ws_bytes, hipStream_t s) {
-  p.zero = nullptr;
-  p.nchunks = rsp_cdiv(p.K, BK);
-  fill_fastdiv(p);
-  p.dmajor = 0;                      // plain (sample, depth, h, w) rows
-  p.tm_skip = 0;
-  fill_fastdiv_linear(p);
-  p.m_tiles = rsp_cdiv(p.M, 128);
-  p.n_tiles = rsp_cdiv(p.Cout, 64);
-  DirectPlan dp = direct_plan(p.M, p.Cout, p.nchunks);
-  if (dp.splitk > 1 && (!workspace || ws_bytes < (size_t)dp.splitk * (size_t)p.M * p.Cout * sizeof(float))) dp = {1, p.nchunks};
-  p.splitk = dp.splitk;
-  p.chunks_per_split = dp.cps;
-  p.full_tiles = 0;
-  p.tail_row0 = 0;
-  p.partial = p.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
-  rsp_note_kernel("igemm_direct_kernel");
-  hipLaunchKernelGGL(igemm_direct_kernel, dim3((unsigned)(p.m_tiles * p.n_tiles * p.splitk)), dim3(256), 0, s, p);
-  int rc = rsp_check_launch("igemm_direct_kernel");
-  if (rc != RSP_OK) return rc;
-  if (p.splitk > 1) {
-    ReduceParams r;
-    fill_reduce(r, p);
-    dim3 grid(rsp_cdiv(p.M, 128), rsp_cdiv(p.Cout, 64));
-    if (p.Cout % 4 == 0 && p.out_ld % 4 == 0 && rsp_aligned16(p.y) && (!p.bias || rsp_aligned16(p.bias)))
-      hipLaunchKernelGGL(splitk_reduce_vec_kernel, grid, dim3(256), 0, s, r);
-    else
-      hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, s, r);
-    rc = rsp_check_launch("splitk_reduce_kernel");
-  }
-  return rc;
+// byte offset of the last output row from the output base pointer; + a segment's columns: the bytes reachable from it
+static unsigned long long out_span_bytes(const IgemmParams& p) {
+  return ((unsigned long long)p.Nb * p.oDm * p.oHm * p.oWm - 1) * (unsigned long long)p.out_ld * 4ull;
+}
+constexpr unsigned long long Y_NOT_32BIT = ~0ull >> 1;      // a span the queries pass for "output beyond 32-bit offsets"
+static unsigned out_extent_bytes(unsigned long long y_span, int cols) {
+  const unsigned long long b = y_span + (unsigned long long)cols * 4ull;
+  return b < 0x7ffffff0ull ? (unsigned)b : 0u;      // (< 2 GiB: an offset with bit 31 set is out of range whatever is added to it); 0 if more
 }
 
+// The plan of one column segment (`nb`: narrow_bn of the whole GEMM).  ws_bytes: the workspace the launch may use — a K split that
+// needs more degrades gracefully to the unsplit plan, still correct (the workspace queries plan with SIZE_MAX and read the need).
+LaunchPlan plan_segment(long long M, int c0, int cols, int nb, int nchunks, bool kmajor, bool vec4, bool y32, size_t ws_bytes) {
+  LaunchPlan l = {};
+  l.c0 = c0; l.cols = cols; l.bn_narrow = nb;
+  int bn = nb ? nb : tile_bn(cols);
+  if (!vec4 && (bn == 160 || bn == 96)) bn = 128;      // the scalar-gather fallback only has the power-of-two tiles
+  // rows per tile: 256 on the tall 64-wide instance of the persistent kernel (tall_tiles), which needs 32-bit output offsets;
+  // else 128 (stat partials are defined on 128-row tiles)
+  const int bm = (tall_tiles(M, bn, vec4) && persist_enabled() && y32) ? 256 : 128;
+  const int m_tiles = rsp_cdiv(M, bm), n_tiles = rsp_cdiv(cols, bn);
+  SplitPlan sp = plan_split(m_tiles, n_tiles, bn, vec4, nchunks, cols, bm);
+  l.nbuf = (bm == 256 || single_buffer(m_tiles, n_tiles, bn, vec4)) ? 1 : 2;
+  if (sp.splitk > 1 && ws_bytes < split_partial_bytes(sp, M, n_tiles, cols, bm)) sp = {m_tiles * n_tiles, 1, nchunks};
+  l.full_tiles = sp.full_tiles;
+  l.splitk = sp.splitk;
+  l.chunks_per_split = sp.cps;
+  l.tail_row0 = sp.full_tiles / n_tiles * bm;
+  l.partial_bytes = split_partial_bytes(sp, M, n_tiles, cols, bm);
+  // (the long tap-major 128-wide launches — C3D conv2: 54 chunks per tile — measured 1 % faster on the per-tile kernel; everything
+  //  else equal or better persistent: R3D-18 +2.9 %, R(2+1)D / S3D-G +0.3 % per step, profiles/r04/experiments_r4.txt)
+  const bool long_tm128 = !kmajor && bn == 128 && nchunks >= 48;
+  const bool persist = vec4 && persist_enabled() && !long_tm128 && y32 && (l.splitk == 1 || l.partial_bytes < 0x7ffffff0ull);
+  // the persistent 64-wide tile is compiled for four waves per SIMD (121-128 VGPRs): with ONE tile buffer (24.5 KB) four workgroups
+  // share a CU on launches of at least one such round (R3D-18 +0.5 %, R(2+1)D +0.2 % per step); the per-tile 64-wide kernel, three
+  // per CU either way, lost 9 % to the extra barrier (single_buffer)
+  if (persist && bm == 128 && bn == 64 && (long long)m_tiles * n_tiles >= 1024) l.nbuf = 1;
+  l.bm = bm;
+  const bool square = bm == 128 && (bn == 128 || bn == 64);      // 2 x 2 waves; every other tile: four waves stacked along M
+  l.waves_m = square ? 2 : 4;
+  l.waves_n = square ? 2 : 1;
+  if (persist) {
+    const bool fold = kmajor && bm == 128 && bn == 128 && two_level_min_chunks() > 0 && nchunks >= two_level_min_chunks();
+    l.family = fold ? K_PERSIST_FOLD : K_PERSIST;
+    l.ks = kmajor;
+    if (bn == 160 && half_block_cols(cols)) bn = 144;
+    l.minw = fold ? FOLD_CHUNKS : persist_minw(bn, bm);
+  } else {
+    l.family = (vec4 && kmajor) ? K_TILE_KS : K_TILE;
+    l.vec = vec4 ? 4 : 1;
+    l.minw = 2;
+  }
+  l.bn = bn;
+  return l;
+}
+
+// THE launch plan of a GEMM description (M, Cout, Cin, K and the tap counts of p).  Besides the description it depends on whether
+// the LDS-DMA path applies (vec4: fill_fwd_params / fill_dgrad_class_params), on whether the output is addressable with 32-bit
+// offsets (y_span: out_span_bytes) and on the workspace available.
+ConvPlan plan_conv(const IgemmParams& p, bool vec4, unsigned long long y_span, size_t ws_bytes) {
+  ConvPlan cp = {};
+  const int nchunks = rsp_cdiv(p.K, BK);
+  if (direct_applies(p.M, p.Cout, p.Cin, p.K, vec4)) {
+    DirectPlan dp = direct_plan(p.M, p.Cout, nchunks);
+    if (dp.splitk > 1 && ws_bytes < direct_partial_bytes(p.M, p.Cout, p.K)) dp = {1, nchunks};
+    LaunchPlan& l = cp.l[0];
+    l.family = K_DIRECT;
+    l.bm = 128; l.bn = 64; l.cols = p.Cout;
+    l.splitk = dp.splitk;
+    l.chunks_per_split = dp.cps;
+    l.partial_bytes = dp.splitk > 1 ? direct_partial_bytes(p.M, p.Cout, p.K) : 0;
+    cp.n = 1;
+    return cp;
+  }
+  const bool kmajor = k_slice_major(p.Cin, p.nTd * p.nTh * p.nTw);
+  const int nb = vec4 ? narrow_bn(p.M, p.Cout, nchunks) : 0;      // one launch of 64- / 32-wide tiles over all columns (no column segments)
+  Segments g = plan_segments(p.Cout);
+  if (nb) g = {1, {0, 0}, {p.Cout, 0}};
+  cp.n = g.n;
+  for (int i = 0; i < g.n; ++i)
+    cp.l[i] = plan_segment(p.M, g.c0[i], g.width[i], nb, nchunks, kmajor, vec4, out_extent_bytes(y_span, g.width[i]) != 0, ws_bytes);
+  return cp;
+}
+
+void launch_reduce(const IgemmParams& p, hipStream_t s) {
+  ReduceParams r;
+  fill_reduce(r, p);
+  dim3 grid(rsp_cdiv(p.M - p.tail_row0, 128), rsp_cdiv(p.Cout, 64));
+  if (p.Cout % 4 == 0 && p.out_ld % 4 == 0 && rsp_aligned16(p.y) && (!p.bias || rsp_aligned16(p.bias)))
+    hipLaunchKernelGGL(splitk_reduce_vec_kernel, grid, dim3(256), 0, s, r);
+  else
+    hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, s, r);
+}
+
+// Execute a plan: copy its fields into the kernel parameters and launch.
 int run_igemm(IgemmParams& p, bool vec4, void* workspace, size_t ws_bytes, hipStream_t s) {
   p.stat_ld = p.Cout;
-  if (direct_applies(p.M, p.Cout, p.Cin, p.K, vec4)) return run_direct(p, workspace, ws_bytes, s);
-  if (const int nb = vec4 ? narrow_bn(p.M, p.Cout, rsp_cdiv(p.K, BK)) : 0) {      // one launch of 64- / 32-wide tiles over all columns (no column segments)
-    p.bn_narrow = nb;
-    return run_igemm_segment(p, vec4, workspace, ws_bytes, s);
-  }
-  const Segments g = plan_segments(p.Cout);
-  if (g.n == 1) return run_igemm_segment(p, vec4, workspace, ws_bytes, s);
-  for (int i = 0; i < g.n; ++i) {
-    IgemmParams q = p;
-    const int c0 = g.c0[i];
-    q.Cout = g.width[i];
-    q.w = p.w + (long long)c0 * p.Kld;
+  const unsigned long long y_span = out_span_bytes(p);
+  const ConvPlan cp = plan_conv(p, vec4, y_span, workspace ? ws_bytes : 0);
+  for (int i = 0; i < cp.n; ++i) {
+    const LaunchPlan& l = cp.l[i];
+    IgemmParams q = p;      // this launch's column segment: operands addressed through offset base pointers
+    q.Cout = l.cols;
+    q.w = p.w + (long long)l.c0 * p.Kld;
     q.w_bytes = (unsigned)((unsigned long long)q.Cout * p.Kld * 4ull);
-    q.bias = p.bias ? p.bias + c0 : nullptr;
-    q.y = p.y + c0;
-    q.stat = p.stat ? p.stat + 2ll * c0 : nullptr;
-    const int rc = run_igemm_segment(q, vec4, workspace, ws_bytes, s);   // same stream: the workspace is free again when it starts
+    q.bias = p.bias ? p.bias + l.c0 : nullptr;
+    q.y = p.y + l.c0;
+    q.stat = p.stat ? p.stat + 2ll * l.c0 : nullptr;
+    q.bn_narrow = l.bn_narrow;
+    q.nchunks = rsp_cdiv(q.K, BK);
+    fill_fastdiv(q);
+    if (!vec4 || l.family == K_DIRECT) {      // plain (sample, depth, h, w) rows: only the LDS-DMA tile kernels know the depth-major
+      q.dmajor = 0;                           // enumeration and the skipping walks
+      q.tm_skip = 0;
+      fill_fastdiv_linear(q);
+    }
+    q.bm = l.bm;
+    q.nbuf = l.nbuf;
+    q.full_tiles = l.full_tiles;
+    q.splitk = l.splitk;
+    q.chunks_per_split = l.chunks_per_split;
+    q.tail_row0 = l.tail_row0;
+    q.partial = l.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;      // (same stream: free again when the next launch starts)
+    int rc;
+    if (l.family == K_DIRECT) {
+      q.m_tiles = rsp_cdiv(q.M, 128);
+      q.n_tiles = rsp_cdiv(q.Cout, 64);
+      rsp_note_kernel(kernel_format(K_DIRECT));
+      hipLaunchKernelGGL(igemm_direct_kernel, dim3((unsigned)(q.m_tiles * q.n_tiles * q.splitk)), dim3(256), 0, s, q);
+      rc = rsp_check_launch("igemm_direct_kernel");
+    } else {
+      q.zero = igemm_zero_page();
+      if (!q.zero) {
+        rsp_set_error("hipGetSymbolAddress(g_zero) failed");
+        return RSP_ELAUNCH;
+      }
+      q.y_bytes = out_extent_bytes(y_span, q.Cout);
+      q.partial_bytes = l.partial_bytes < 0x7ffffff0ull ? (unsigned)l.partial_bytes : 0u;
+      rc = launch_planned(q, l, s);
+    }
     if (rc != RSP_OK) return rc;
+    if (l.splitk > 1) {
+      launch_reduce(q, s);
+      rc = rsp_check_launch("splitk_reduce_kernel");
+      if (rc != RSP_OK) return rc;
+    }
   }
   return RSP_OK;
 }
 
-size_t igemm_partial_bytes_segment(long long M, int Cout, int K);
-
-size_t igemm_partial_bytes(long long M, int Cout, int K) {
-  const Segments g = plan_segments(Cout);
-  size_t best = direct_partial_bytes(M, Cout, K);      // (whether the direct kernel runs depends on alignment, unknown here)
-  if (const int nb = narrow_bn(M, Cout, rsp_cdiv(K, BK))) {
-    const int n_tiles = rsp_cdiv(Cout, nb);
-    const size_t b = split_partial_bytes(plan_split(rsp_cdiv(M, 128), n_tiles, nb, true, rsp_cdiv(K, BK), Cout), M, n_tiles, Cout);
-    best = b > best ? b : best;
-  }
-  for (int i = 0; i < g.n; ++i) {
-    const size_t b = igemm_partial_bytes_segment(M, g.width[i], K);
-    best = b > best ? b : best;
-  }
+// Partial bytes a GEMM may need.  Which of its plans run_igemm takes depends on pointer alignment (LDS-DMA or scalar gather) and on
+// the output's extent (32-bit offsets or not), both unknown to the workspace queries: the largest need over those plans, from the
+// function the launch plans with.
+size_t igemm_partial_bytes(const IgemmParams& p) {
+  size_t best = direct_partial_bytes(p.M, p.Cout, p.K);      // (kept as it was: counted even where the direct kernel is switched off)
+  auto count = [&](const LaunchPlan& l) { best = l.partial_bytes > best ? l.partial_bytes : best; };
+  const ConvPlan plans[2] = {plan_conv(p, true, Y_NOT_32BIT, SIZE_MAX), plan_conv(p, false, 0, SIZE_MAX)};
+  for (const ConvPlan& cp : plans)
+    for (int i = 0; i < cp.n; ++i) count(cp.l[i]);
+  // the column segments on the LDS-DMA path, with and without 32-bit offsets (the 256-row tiles).  Kept as it was in two corners:
+  // they are counted even where one narrow launch replaces them, and a NARROW launch on 256-row tiles (tall_min_tiles > 0, off by
+  // default) is not counted — there a K split may still want more than this and fall back to the unsplit plan.
+  const Segments g = plan_segments(p.Cout);
+  const bool kmajor = k_slice_major(p.Cin, p.nTd * p.nTh * p.nTw);
+  for (int i = 0; i < 2 * g.n; ++i)
+    count(plan_segment(p.M, g.c0[i / 2], g.width[i / 2], 0, rsp_cdiv(p.K, BK), kmajor, true, i % 2 == 0, SIZE_MAX));
   return best;
-}
-
-size_t igemm_partial_bytes_segment(long long M, int Cout, int K) {
-  const int bn = tile_bn(Cout), bn_s = (bn == 160 || bn == 96) ? 128 : bn;     // scalar-gather fallback: power-of-two tiles only
-  const int m_tiles = rsp_cdiv(M, 128), n_tiles = rsp_cdiv(Cout, bn), n_tiles_s = rsp_cdiv(Cout, bn_s);
-  // the gather variant (hence the plan) depends on pointer alignment, unknown here: size for the larger of the two
-  size_t a = split_partial_bytes(plan_split(m_tiles, n_tiles, bn, true, rsp_cdiv(K, BK), Cout), M, n_tiles, Cout);
-  const size_t b = split_partial_bytes(plan_split(m_tiles, n_tiles_s, bn_s, false, rsp_cdiv(K, BK), Cout), M, n_tiles_s, Cout);
-  if (tall_tiles(M, bn, true)) {      // ... or on 256-row tiles (whether they run depends on the output extent, unknown here)
-    const size_t t = split_partial_bytes(plan_split(rsp_cdiv(M, 256), n_tiles, bn, true, rsp_cdiv(K, BK), Cout, 256), M, n_tiles, Cout, 256);
-    a = t > a ? t : a;
-  }
-  return a > b ? a : b;
 }
 
 static inline int mod_pos(int a, int m) { return ((a % m) + m) % m; }
@@ -2550,10 +2585,9 @@ DgradClass dgrad_class(const rsp_conv3d_desc* d, int c) {
 // Host replica of the kernels' walk over K: the share of a problem's (tile, chunk) pairs that igemm_body executes once the chunks
 // whose taps are padding for a whole tile are skipped (1.0 when nothing is skipped).  Same row enumeration (row_decode), same
 // validity bits (span), same liveness tests as the device code; the column segments of one GEMM share the rows, hence the share.
-bool direct_applies(long long M, int Cout, int Cin, int K, bool vec4);
-
-double igemm_live_fraction(IgemmParams p, bool vec4, bool may_direct = true) {
-  if (may_direct && direct_applies(p.M, p.Cout, p.Cin, p.K, vec4)) return 1.0;      // igemm_direct_kernel walks every chunk
+// l: the launch that walks the rows (the first of the GEMM's plan, or the shared launch of a strided input gradient).
+double igemm_live_fraction(IgemmParams p, bool vec4, const LaunchPlan& l) {
+  if (l.family == K_DIRECT) return 1.0;      // igemm_direct_kernel walks every chunk
   p.nchunks = rsp_cdiv(p.K, BK);
   fill_fastdiv(p);
   if (!vec4) return 1.0;
@@ -2565,9 +2599,7 @@ double igemm_live_fraction(IgemmParams p, bool vec4, bool may_direct = true) {
     const int lo = std::min(std::max(0, -c), 8), hi = std::min(nT - 1, D - 1 - c);
     return hi >= lo ? (2u << hi) - (1u << lo) : 0u;
   };
-  // (rows per tile as run_igemm / run_igemm_segment choose them; 32-bit output offsets assumed)
-  const int nbw = narrow_bn(p.M, p.Cout, p.nchunks);
-  const int bm = (persist_enabled() && tall_tiles(p.M, nbw ? nbw : tile_bn(plan_segments(p.Cout).width[0]), vec4)) ? 256 : 128;
+  const int bm = l.bm;
   const int ntaps = p.nTd * p.nTh * p.nTw, m_tiles = rsp_cdiv(p.M, bm);
   long long live = 0;
   for (int mt = 0; mt < m_tiles; ++mt) {
@@ -2668,7 +2700,89 @@ static bool fill_dgrad_class_params(const rsp_conv3d_desc* d, const DgradClass& 
                  wb < (1ull << 32) && g.nt <= 8 && g.nh <= 8 && g.nw <= 8;
 }
 
+float* const ALIGNED = reinterpret_cast<float*>(uintptr_t(1) << 20);      // stands for any 16-byte aligned tensor (the host queries)
+
+// The per-class GEMM descriptions of an input gradient over packed per-class weights (class c's block follows class c-1's, O x Kld
+// floats each); empty classes are left out.  Returns their number.
+static int dgrad_classes(const rsp_conv3d_desc* d, const float* dy, const float* wpk, float* dx, IgemmParams* cls, bool* cvec) {
+  int ncls = 0;
+  size_t woff = 0;
+  for (int c = 0; c < d->sT * d->sH * d->sW; ++c) {
+    const DgradClass g = dgrad_class(d, c);
+    if (g.nt * g.nh * g.nw == 0 || g.Gd * g.Gh * g.Gw == 0) continue;
+    cvec[ncls] = fill_dgrad_class_params(d, g, dy, wpk + woff, dx, cls[ncls]);
+    woff += (size_t)d->Cin * cls[ncls].Kld;
+    ++ncls;
+  }
+  return ncls;
+}
+
+// Small classes of a strided convolution share ONE launch (igemm_multi_kernel): the classes on the LDS-DMA path with the
+// tap-major K walk (one walk per launch; a class long enough for the slice-major walk — R3D-18 layer4.0's 8-tap class — runs on
+// its own behind them), a single column segment, and few enough tiles that separate launches would each leave most of the
+// machine idle (above a few thousand tiles each class fills the machine on its own).
+// Few tiles (R3D-18 layer3.0 / layer4.0: 8 classes of 25 / 8 tiles): the classes still share ONE launch, each cut along K by one
+// common plan, and ONE batched reduce sums all of them (round 5; until then each class ran its own K-split launch + reduce: 16
+// dependent launches of 10-15 us for 3.6 GFLOP).  may_split: multi_split_ok, or true for the workspace query.
+struct MultiPlan {
+  int n;                  // classes that share the launch (0: no shared launch)
+  int cls[MAX_MULTI];     // ... as indices into the non-empty classes
+  LaunchPlan l;
+  bool split;
+  MultiSplit ms;
+};
+static bool multi_split_ok(const rsp_conv3d_desc* d, const float* dx) {      // the batched reduce writes float4 rows of dx
+  return multi_split_enabled() && d->Cin % 4 == 0 && d->in_ld % 4 == 0 && rsp_aligned16(dx);
+}
+static MultiPlan plan_multi(const IgemmParams* cls, const bool* cvec, int ncls, bool may_split, size_t ws_bytes) {
+  MultiPlan mp = {};
+  const int cols = ncls ? cls[0].Cout : 0, bn = tile_bn(cols);
+  if (ncls < 2 || plan_segments(cols).n != 1) return mp;
+  int nm = 0;
+  for (int i = 0; i < ncls; ++i) {
+    if (!cvec[i] || k_slice_major(cls[i].Cin, cls[i].nTd * cls[i].nTh * cls[i].nTw)) continue;
+    if (nm == MAX_MULTI) return mp;
+    mp.cls[nm++] = i;
+  }
+  if (nm < 2) return mp;
+  long long Ms[MAX_MULTI], tiles_all = 0;
+  int tl[MAX_MULTI], nc[MAX_MULTI];
+  for (int j = 0; j < nm; ++j) {
+    Ms[j] = cls[mp.cls[j]].M;
+    tl[j] = rsp_cdiv(Ms[j], 128) * rsp_cdiv(cols, bn);
+    nc[j] = rsp_cdiv(cls[mp.cls[j]].K, BK);
+    tiles_all += tl[j];
+  }
+  mp.split = may_split && tiles_all < 512;
+  if (mp.split) {
+    mp.ms = plan_multi_split(nm, Ms, tl, nc, cols);
+    if (mp.ms.bytes > ws_bytes) mp.split = false;      // degrade gracefully: the classes run one by one
+  }
+  if (!((tiles_all >= 512 && tiles_all <= 4096) || mp.split)) return mp;
+  mp.n = nm;
+  const bool square = bn == 128 || bn == 64;
+  mp.l.family = K_MULTI;
+  mp.l.bm = 128; mp.l.bn = bn; mp.l.waves_m = square ? 2 : 4; mp.l.waves_n = square ? 2 : 1; mp.l.vec = 4; mp.l.minw = 2;
+  mp.l.cols = cols;
+  mp.l.partial_bytes = mp.split ? mp.ms.bytes : 0;
+  return mp;
+}
+
 }  // namespace
+
+// A descriptor every convolution pass accepts (conv_stem.h: shared with conv_wgrad.hip).
+bool rsp_conv_desc_ok(const rsp_conv3d_desc* d) {
+  if (!d) return false;
+  if (d->N <= 0 || d->Cin <= 0 || d->Cout <= 0) return false;
+  if (d->kT * d->kH * d->kW > MAX_TAPS || d->kT <= 0 || d->kH <= 0 || d->kW <= 0) return false;
+  if (d->sT <= 0 || d->sH <= 0 || d->sW <= 0 || d->pT < 0 || d->pH < 0 || d->pW < 0) return false;
+  if (d->Do != (d->Di + 2 * d->pT - d->kT) / d->sT + 1) return false;
+  if (d->Ho != (d->Hi + 2 * d->pH - d->kH) / d->sH + 1) return false;
+  if (d->Wo != (d->Wi + 2 * d->pW - d->kW) / d->sW + 1) return false;
+  if (d->Do <= 0 || d->Ho <= 0 || d->Wo <= 0) return false;
+  if (d->in_ld < d->Cin || d->out_ld < d->Cout) return false;
+  return (long long)d->N * d->Do * d->Ho * d->Wo < (1ll << 31);
+}
 
 extern "C" {
 
@@ -2707,7 +2821,9 @@ int32_t rsp_conv3d_stat_tiles(const rsp_conv3d_desc* d) {
 size_t rsp_conv3d_fwd_workspace(const rsp_conv3d_desc* d) {
   if (!desc_ok(d)) return 0;
   if (rsp_stem_applicable(d)) return 0;
-  return igemm_partial_bytes((long long)d->N * d->Do * d->Ho * d->Wo, d->Cout, d->kT * d->kH * d->kW * d->Cin);
+  IgemmParams p;
+  fill_fwd_params(d, ALIGNED, ALIGNED, nullptr, ALIGNED, nullptr, p);
+  return igemm_partial_bytes(p);
 }
 
 int rsp_conv3d_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed, const float* bias, float* y,
@@ -2726,24 +2842,25 @@ int rsp_conv3d_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_pack
 // after skipping the K chunks / row chunks that are zero padding for a whole tile.  which: 0 forward, 1 dgrad, 2 wgrad.
 double rsp_conv3d_executed_fraction(const rsp_conv3d_desc* d, int which) {
   if (!desc_ok(d)) return 1.0;
-  float* const al = reinterpret_cast<float*>(uintptr_t(1) << 20);      // stands for any 16-byte aligned tensor
   if (which == 2) return rsp_wgrad_executed_fraction(d);
+  // (16-byte aligned tensors and 32-bit output offsets assumed; the O(rows) walk is this query's alone, never the launch path's)
   if (which == 0) {
     if (rsp_stem_applicable(d)) return 1.0;
     IgemmParams p;
-    const bool vec4 = fill_fwd_params(d, al, al, nullptr, al, nullptr, p);
-    return igemm_live_fraction(p, vec4);
+    const bool vec4 = fill_fwd_params(d, ALIGNED, ALIGNED, nullptr, ALIGNED, nullptr, p);
+    return igemm_live_fraction(p, vec4, plan_conv(p, vec4, 0, SIZE_MAX).l[0]);
   }
-  double live = 0.0, tot = 0.0;
+  IgemmParams cls[64];
+  bool cvec[64], in_multi[64] = {false};
+  const int ncls = dgrad_classes(d, ALIGNED, ALIGNED, ALIGNED, cls, cvec);
   // (the tap-major classes that share one igemm_multi_kernel launch run the tile kernels' walk, whatever their size: dgrad_run)
-  const bool multi = strstr(rsp_conv3d_kernel_name(d, 1), "igemm_multi_kernel") != nullptr;
-  for (int c = 0; c < d->sT * d->sH * d->sW; ++c) {
-    const DgradClass g = dgrad_class(d, c);
-    if (g.nt * g.nh * g.nw == 0 || g.Gd * g.Gh * g.Gw == 0) continue;
-    IgemmParams p;
-    const bool vec4 = fill_dgrad_class_params(d, g, al, al, al, p);
+  const MultiPlan mp = plan_multi(cls, cvec, ncls, multi_split_ok(d, ALIGNED), SIZE_MAX);
+  for (int j = 0; j < mp.n; ++j) in_multi[mp.cls[j]] = true;
+  double live = 0.0, tot = 0.0;
+  for (int i = 0; i < ncls; ++i) {
+    const IgemmParams& p = cls[i];
     const double wgt = (double)p.M * p.K;
-    live += wgt * igemm_live_fraction(p, vec4, !(multi && !k_slice_major(d->Cout, g.nt * g.nh * g.nw)));
+    live += wgt * igemm_live_fraction(p, cvec[i], in_multi[i] ? mp.l : plan_conv(p, cvec[i], 0, SIZE_MAX).l[0]);
     tot += wgt;
   }
   return tot > 0 ? live / tot : 1.0;
@@ -2762,147 +2879,50 @@ const char* rsp_conv3d_kernel_name(const rsp_conv3d_desc* d, int which) {
   if (!desc_ok(d)) return "invalid";
   if (which == 2) return rsp_wgrad_kernel_name(d);
   if (which == 0 && rsp_stem_applicable(d)) return rsp_stem_kernel_name(d);
-  const int cin = which == 0 ? d->Cin : d->Cout, ld = which == 0 ? d->in_ld : d->out_ld, cols = which == 0 ? d->Cout : d->Cin;
-  const bool vec4 = cin % 4 == 0 && ld % 4 == 0 && d->kT <= 8 && d->kH <= 8 && d->kW <= 8;
-  if (which == 1 && vec4 && d->sT * d->sH * d->sW > 1 && plan_segments(cols).n == 1) {
-    // the tap-major stride-parity classes of a small or mid-sized strided dgrad share one launch, which runs first (dgrad_run)
-    int nm = 0;
-    long long tiles = 0;
-    for (int c = 0; c < d->sT * d->sH * d->sW; ++c) {
-      const DgradClass g = dgrad_class(d, c);
-      if (g.nt * g.nh * g.nw == 0 || g.Gd * g.Gh * g.Gw == 0 || k_slice_major(d->Cout, g.nt * g.nh * g.nw)) continue;
-      ++nm;
-      tiles += (long long)rsp_cdiv(d->N * g.Gd * g.Gh * g.Gw, 128) * rsp_cdiv(cols, tile_bn(cols));
-    }
-    if (nm >= 2 && nm <= MAX_MULTI && ((tiles >= 512 && tiles <= 4096) || (tiles < 512 && multi_split_enabled() && cols % 4 == 0 &&
-                                                                         (which == 0 ? d->out_ld : d->in_ld) % 4 == 0))) {
-      switch (tile_bn(cols)) {
-        case 160: return "igemm_multi_kernel<128, 160, 4, 1, 4, 2>";
-        case 128: return "igemm_multi_kernel<128, 128, 2, 2, 4, 2>";
-        case 96: return "igemm_multi_kernel<128, 96, 4, 1, 4, 2>";
-        case 64: return "igemm_multi_kernel<128, 64, 2, 2, 4, 2>";
-        default: return "igemm_multi_kernel<128, 32, 4, 1, 4, 2>";
-      }
-    }
+  static thread_local char names[64][64];      // the few dozen instance names, formatted once each
+  static thread_local int n_names = 0;
+  LaunchPlan l;
+  if (which == 0) {
+    IgemmParams p;
+    const bool vec4 = fill_fwd_params(d, ALIGNED, ALIGNED, nullptr, ALIGNED, nullptr, p);
+    l = plan_conv(p, vec4, out_span_bytes(p), SIZE_MAX).l[0];      // (two column segments: named after the first, wider one)
+  } else {
+    // the shared launch of the tap-major stride-parity classes runs first if there is one (dgrad_run), else the first non-empty class
+    IgemmParams cls[64];
+    bool cvec[64];
+    const int ncls = dgrad_classes(d, ALIGNED, ALIGNED, ALIGNED, cls, cvec);
+    const MultiPlan mp = plan_multi(cls, cvec, ncls, multi_split_ok(d, ALIGNED), SIZE_MAX);
+    // (kept as it was: a strided input gradient that runs class by class is spelled with the tap-major K walk, whatever the walk
+    //  its first class runs with)
+    if (d->sT * d->sH * d->sW > 1) cls[0].nTd = cls[0].nTh = cls[0].nTw = 1;
+    l = mp.n ? mp.l : plan_conv(cls[0], cvec[0], out_span_bytes(cls[0]), SIZE_MAX).l[0];
   }
-  {
-    // small launches: the direct kernel (run_igemm).  dgrad: the first non-empty stride-parity class decides, as below
-    long long Mrows = (long long)d->N * d->Do * d->Ho * d->Wo;
-    int Kk = d->kT * d->kH * d->kW * d->Cin;
-    if (which == 1) {
-      for (int c = 0; c < d->sT * d->sH * d->sW; ++c) {
-        const DgradClass g = dgrad_class(d, c);
-        if (g.nt * g.nh * g.nw == 0 || g.Gd * g.Gh * g.Gw == 0) continue;
-        Mrows = (long long)d->N * g.Gd * g.Gh * g.Gw;
-        Kk = g.nt * g.nh * g.nw * d->Cout;
-        break;
-      }
-    }
-    if (direct_applies(Mrows, cols, cin, Kk, vec4)) return "igemm_direct_kernel";
-  }
-  // (a convolution that runs as two column segments is named after the first, wider one)
-  int bn = tile_bn(plan_segments(cols).width[0]);
-  if (!vec4 && (bn == 160 || bn == 96)) bn = 128;
-  long long Mrows = (long long)d->N * d->Do * d->Ho * d->Wo;
-  int kchunks = rsp_cdiv((long long)d->kT * d->kH * d->kW * d->Cin, BK);
-  if (which == 1) {      // the first non-empty stride-parity class (its launch is the one rsp_last_conv_kernel reports)
-    for (int c = 0; c < d->sT * d->sH * d->sW; ++c) {
-      const DgradClass g = dgrad_class(d, c);
-      if (g.nt * g.nh * g.nw == 0 || g.Gd * g.Gh * g.Gw == 0) continue;
-      Mrows = (long long)d->N * g.Gd * g.Gh * g.Gw;
-      kchunks = rsp_cdiv((long long)g.nt * g.nh * g.nw * d->Cout, BK);
-      break;
-    }
-  }
-  if (vec4) {
-    const int nb = narrow_bn(Mrows, cols, kchunks);
-    if (nb) bn = nb;
-  }
-  // spelled as rocprofv3 prints the demangled instance (minus namespace and argument list)
-  const bool ks = vec4 && ((which == 0 && k_slice_major(d->Cin, d->kT * d->kH * d->kW)) ||
-                           (which == 1 && d->sT * d->sH * d->sW == 1 && k_slice_major(d->Cout, d->kT * d->kH * d->kW)));
-  // output addressable with 32-bit offsets: the persistent instances (launch_persist)
-  const unsigned long long out_b = which == 0 ? (unsigned long long)d->N * d->Do * d->Ho * d->Wo * d->out_ld * 4ull
-                                              : (unsigned long long)d->N * d->Di * d->Hi * d->Wi * d->in_ld * 4ull;
-  if (vec4 && persist_enabled() && out_b < 0x7ffffff0ull && tall_tiles(Mrows, bn, vec4))
-    return ks ? "igemm_persist_kernel<256, 64, 4, 1, true, 3>" : "igemm_persist_kernel<256, 64, 4, 1, false, 3>";
-  const bool long_tm128 = !ks && bn == 128 && kchunks >= 48;      // as in run_igemm_segment
-  if (vec4 && persist_enabled() && !long_tm128 && out_b < 0x7ffffff0ull) {
-    if (ks) {
-      if (bn == 128 && two_level_min_chunks() > 0 && kchunks >= two_level_min_chunks()) return "igemm_persist_fold_kernel<128, 128, 2, 2, true, 16>";
-      switch (bn) {
-        case 160: return half_block_cols(cols) ? "igemm_persist_kernel<128, 144, 4, 1, true, 2>" : "igemm_persist_kernel<128, 160, 4, 1, true, 2>";
-        case 128: return "igemm_persist_kernel<128, 128, 2, 2, true, 3>";
-        case 96: return "igemm_persist_kernel<128, 96, 4, 1, true, 3>";
-        case 64: return "igemm_persist_kernel<128, 64, 2, 2, true, 4>";
-        default: return "igemm_persist_kernel<128, 32, 4, 1, true, 4>";
-      }
-    }
-    switch (bn) {
-      case 160: return half_block_cols(cols) ? "igemm_persist_kernel<128, 144, 4, 1, false, 2>" : "igemm_persist_kernel<128, 160, 4, 1, false, 2>";
-      case 128: return "igemm_persist_kernel<128, 128, 2, 2, false, 3>";
-      case 96: return "igemm_persist_kernel<128, 96, 4, 1, false, 3>";
-      case 64: return "igemm_persist_kernel<128, 64, 2, 2, false, 4>";
-      default: return "igemm_persist_kernel<128, 32, 4, 1, false, 4>";
-    }
-  }
-  if (ks) {
-    switch (bn) {
-      case 160: return "igemm_ks_kernel<128, 160, 4, 1>";
-      case 128: return "igemm_ks_kernel<128, 128, 2, 2>";
-      case 96: return "igemm_ks_kernel<128, 96, 4, 1>";
-      case 64: return "igemm_ks_kernel<128, 64, 2, 2>";
-      default: return "igemm_ks_kernel<128, 32, 4, 1>";
-    }
-  }
-  if (vec4) {
-    switch (bn) {
-      case 160: return "igemm_kernel<128, 160, 4, 1, 4, 2>";
-      case 128: return "igemm_kernel<128, 128, 2, 2, 4, 2>";
-      case 96: return "igemm_kernel<128, 96, 4, 1, 4, 2>";
-      case 64: return "igemm_kernel<128, 64, 2, 2, 4, 2>";
-      default: return "igemm_kernel<128, 32, 4, 1, 4, 2>";
-    }
-  }
-  return bn == 128 ? "igemm_kernel<128, 128, 2, 2, 1, 2>" : (bn == 64 ? "igemm_kernel<128, 64, 2, 2, 1, 2>" : "igemm_kernel<128, 32, 4, 1, 1, 2>");
+  char name[64];
+  if (l.family == K_PERSIST || l.family == K_PERSIST_FOLD)
+    snprintf(name, sizeof name, kernel_format(l.family), l.bm, l.bn, l.waves_m, l.waves_n, l.ks ? "true" : "false", l.minw);
+  else
+    snprintf(name, sizeof name, kernel_format(l.family), l.bm, l.bn, l.waves_m, l.waves_n, l.vec, l.minw);
+  for (int i = 0; i < n_names; ++i)
+    if (!strcmp(names[i], name)) return names[i];
+  if (n_names == 64) n_names = 0;
+  return strcpy(names[n_names++], name);
 }
 
 // ---- dgrad ----------------------------------------------------------------------------------------------------
 // dx[i] = sum_{k : (i + p - k) % s == 0} dy[(i + p - k)/s] * w[k]; positions are split into s^3 parity classes,
 // each a dense stride-1 "conv" over dy with its own tap subset; class c writes the strided sub-grid i = s*g + r.
-// partial bytes a descriptor's dgrad may need on the shared K-split launch (alignment-dependent conditions assumed true)
-static size_t dgrad_multi_split_bytes(const rsp_conv3d_desc* d) {
-  const int nclass = d->sT * d->sH * d->sW;
-  if (nclass < 2 || plan_segments(d->Cin).n != 1) return 0;
-  long long Ms[MAX_MULTI], tiles_all = 0;
-  int tl[MAX_MULTI], nc[MAX_MULTI], n = 0;
-  const int bn = tile_bn(d->Cin);
-  for (int c = 0; c < nclass; ++c) {
-    const DgradClass g = dgrad_class(d, c);
-    if (g.nt * g.nh * g.nw == 0 || g.Gd * g.Gh * g.Gw == 0 || k_slice_major(d->Cout, g.nt * g.nh * g.nw)) continue;
-    if (n >= MAX_MULTI) return 0;
-    Ms[n] = (long long)d->N * g.Gd * g.Gh * g.Gw;
-    tl[n] = rsp_cdiv(Ms[n], 128) * rsp_cdiv(d->Cin, bn);
-    nc[n] = rsp_cdiv((long long)g.nt * g.nh * g.nw * d->Cout, BK);
-    tiles_all += tl[n];
-    ++n;
-  }
-  if (n < 2 || tiles_all >= 512) return 0;
-  return plan_multi_split(n, Ms, tl, nc, d->Cin).bytes;
-}
-
 size_t rsp_conv3d_dgrad_workspace(const rsp_conv3d_desc* d) {
   if (!desc_ok(d)) return 0;
-  size_t part = 0;
-  const int nclass = d->sT * d->sH * d->sW;
-  for (int c = 0; c < nclass; ++c) {
-    const DgradClass g = dgrad_class(d, c);
-    if (g.nt * g.nh * g.nw == 0 || g.Gd * g.Gh * g.Gw == 0) continue;
-    const size_t b = igemm_partial_bytes((long long)d->N * g.Gd * g.Gh * g.Gw, d->Cin, g.nt * g.nh * g.nw * d->Cout);
+  IgemmParams cls[64];
+  bool cvec[64];
+  const int ncls = dgrad_classes(d, ALIGNED, ALIGNED, ALIGNED, cls, cvec);
+  // the shared K-split launch of the classes (its alignment-dependent conditions and the A/B switch assumed true), or each class on its own
+  for (int i = 0; i < ncls; ++i) cvec[i] = true;
+  size_t part = plan_multi(cls, cvec, ncls, true, SIZE_MAX).l.partial_bytes;
+  for (int i = 0; i < ncls; ++i) {
+    const size_t b = igemm_partial_bytes(cls[i]);
     part = b > part ? b : part;
   }
-  const size_t mb = dgrad_multi_split_bytes(d);
-  part = mb > part ? mb : part;
   return dgrad_wpack_bytes(d) + part;
 }
 
@@ -2955,54 +2975,13 @@ static int dgrad_run(const rsp_conv3d_desc* d, const float* dy, const float* wpk
     const int rc = zero_rows(dx, rows, d->Cin, d->in_ld, s);
     if (rc != RSP_OK) return rc;
   }
-  // per-class GEMM descriptions
+  // per-class GEMM descriptions and the plan of their shared launch, if any
   IgemmParams cls[64];
   bool cvec[64];
-  int ncls = 0, max_taps = 0;
-  size_t woff = 0;
-  for (int c = 0; c < nclass; ++c) {
-    const DgradClass g = dgrad_class(d, c);
-    if (g.nt * g.nh * g.nw == 0 || g.Gd * g.Gh * g.Gw == 0) continue;
-    const int Kld = (int)rsp_align_up((size_t)g.nt * g.nh * g.nw * d->Cout, 4);
-    IgemmParams& p = cls[ncls];
-    cvec[ncls] = fill_dgrad_class_params(d, g, dy, wpk + woff, dx, p);
-    max_taps = max_taps > g.nt * g.nh * g.nw ? max_taps : g.nt * g.nh * g.nw;
-    woff += (size_t)d->Cin * Kld;
-    ++ncls;
-  }
-  // Small classes of a strided convolution share ONE launch (igemm_multi_kernel): the classes on the LDS-DMA path with the
-  // tap-major K walk (one walk per launch; a class long enough for the slice-major walk — R3D-18 layer4.0's 8-tap class — runs on
-  // its own behind them), a single column segment, and few enough tiles that separate launches would each leave most of the
-  // machine idle.
-  int mi[MAX_MULTI + 1], nm = 0;      // the classes that share the launch
+  const int ncls = dgrad_classes(d, dy, wpk, dx, cls, cvec);
+  const MultiPlan mp = plan_multi(cls, cvec, ncls, multi_split_ok(d, dx), part ? part_bytes : 0);
   bool in_multi[64] = {false};
-  long long tiles_all = 0;
-  const int bn = tile_bn(d->Cin);
-  if (ncls >= 2 && plan_segments(d->Cin).n == 1) {
-    for (int i = 0; i < ncls; ++i)
-      if (cvec[i] && !k_slice_major(cls[i].Cin, cls[i].nTd * cls[i].nTh * cls[i].nTw) && nm <= MAX_MULTI) mi[nm++] = i;
-    if (nm > MAX_MULTI) nm = 0;
-    for (int j = 0; j < nm; ++j) tiles_all += (long long)rsp_cdiv(cls[mi[j]].M, 128) * rsp_cdiv(d->Cin, bn);
-  }
-  const bool multi = nm >= 2;
-  // (above a few thousand tiles each class fills the machine on its own)
-  // Few tiles (R3D-18 layer3.0 / layer4.0: 8 classes of 25 / 8 tiles): the classes still share ONE launch, each cut along K by one
-  // common plan, and ONE batched reduce sums all of them (round 5; until then each class ran its own K-split launch + reduce: 16
-  // dependent launches of 10-15 us for 3.6 GFLOP)
-  bool split_multi = multi && multi_split_enabled() && tiles_all < 512 && d->Cin % 4 == 0 && d->in_ld % 4 == 0 && rsp_aligned16(dx);
-  MultiSplit msp;
-  if (split_multi) {
-    long long Ms[MAX_MULTI];
-    int tl[MAX_MULTI], nc[MAX_MULTI];
-    for (int j = 0; j < nm; ++j) {
-      Ms[j] = cls[mi[j]].M;
-      tl[j] = rsp_cdiv(cls[mi[j]].M, 128) * rsp_cdiv(d->Cin, bn);
-      nc[j] = rsp_cdiv(cls[mi[j]].K, BK);
-    }
-    msp = plan_multi_split(nm, Ms, tl, nc, d->Cin);
-    if (msp.bytes > part_bytes || (msp.bytes && !part)) split_multi = false;
-  }
-  if (multi && ((tiles_all >= 512 && tiles_all <= 4096) || split_multi)) {
+  if (mp.n) {
     const float* zero_page = igemm_zero_page();
     if (!zero_page) {
       rsp_set_error("hipGetSymbolAddress(g_zero) failed");
@@ -3010,11 +2989,11 @@ static int dgrad_run(const rsp_conv3d_desc* d, const float* dy, const float* wpk
     }
     IgemmMulti m;
     memset(&m, 0, sizeof m);
-    m.n = nm;
+    m.n = mp.n;
     int multi_taps = 0;
-    for (int j = 0; j < nm; ++j) {
-      IgemmParams& p = cls[mi[j]];
-      in_multi[mi[j]] = true;
+    for (int j = 0; j < mp.n; ++j) {
+      IgemmParams& p = cls[mp.cls[j]];
+      in_multi[mp.cls[j]] = true;
       const int taps = p.nTd * p.nTh * p.nTw;
       multi_taps = multi_taps > taps ? multi_taps : taps;
       p.zero = zero_page;
@@ -3022,26 +3001,26 @@ static int dgrad_run(const rsp_conv3d_desc* d, const float* dy, const float* wpk
       p.nchunks = rsp_cdiv(p.K, BK);
       fill_fastdiv(p);
       p.m_tiles = rsp_cdiv(p.M, 128);
-      p.n_tiles = rsp_cdiv(p.Cout, bn);
+      p.n_tiles = rsp_cdiv(p.Cout, mp.l.bn);
       p.full_tiles = p.m_tiles * p.n_tiles;
       p.splitk = 1;
       p.nbuf = 2;
       p.chunks_per_split = p.nchunks;
       p.tail_row0 = p.m_tiles * 128;
       int units = p.full_tiles;
-      if (split_multi && msp.S[j] > 1) {      // every tile of this class is a "tail" tile cut into S slices (igemm_body)
+      if (mp.split && mp.ms.S[j] > 1) {      // every tile of this class is a "tail" tile cut into S slices (igemm_body)
         p.full_tiles = 0;
-        p.splitk = msp.S[j];
-        p.chunks_per_split = msp.cps[j];
+        p.splitk = mp.ms.S[j];
+        p.chunks_per_split = mp.ms.cps[j];
         p.tail_row0 = 0;
-        p.partial = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(part) + msp.off[j]);
+        p.partial = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(part) + mp.ms.off[j]);
         units = p.m_tiles * p.n_tiles * p.splitk;
       }
       m.p[j] = p;
       m.start[j + 1] = m.start[j] + units;
     }
     int rc;
-    switch (bn) {
+    switch (mp.l.bn) {
       case 160: rc = launch_multi_cfg<128, 160, 4, 1, 4>(m, multi_taps, s); break;
       case 128: rc = launch_multi_cfg<128, 128, 2, 2, 4>(m, multi_taps, s); break;
       case 96: rc = launch_multi_cfg<128, 96, 4, 1, 4>(m, multi_taps, s); break;
@@ -3049,21 +3028,20 @@ static int dgrad_run(const rsp_conv3d_desc* d, const float* dy, const float* wpk
       default: rc = launch_multi_cfg<128, 32, 4, 1, 4>(m, multi_taps, s); break;
     }
     if (rc != RSP_OK) return rc;
-    if (split_multi && msp.bytes != 0) {
+    if (mp.split && mp.ms.bytes != 0) {
       ReduceMulti rm;
       memset(&rm, 0, sizeof rm);
-      rm.n = nm;
+      rm.n = mp.n;
       int max_mt = 1;
-      for (int j = 0; j < nm; ++j) {
+      for (int j = 0; j < mp.n; ++j) {
         fill_reduce(rm.r[j], m.p[j]);
         if (m.p[j].splitk > 1 && m.p[j].m_tiles > max_mt) max_mt = m.p[j].m_tiles;
       }
-      hipLaunchKernelGGL(splitk_reduce_vec_multi_kernel, dim3(max_mt, rsp_cdiv(d->Cin, 64), nm), dim3(256), 0, s, rm);
+      hipLaunchKernelGGL(splitk_reduce_vec_multi_kernel, dim3(max_mt, rsp_cdiv(d->Cin, 64), mp.n), dim3(256), 0, s, rm);
       rc = rsp_check_launch("splitk_reduce_vec_multi_kernel");
       if (rc != RSP_OK) return rc;
     }
   }
-  (void)max_taps;
   // the rest one by one (same stream: the workspace is free again when each starts)
   for (int i = 0; i < ncls; ++i) {
     if (in_multi[i]) continue;

@@ -3,6 +3,8 @@
 #pragma once
 #include "common.h"
 
+// a valid descriptor as far as every pass (forward, dgrad, wgrad) is concerned: sizes, output dims, pitches, 31-bit row count (conv_igemm.hip)
+bool rsp_conv_desc_ok(const rsp_conv3d_desc* d);
 // true when rsp_conv3d_{packed_fwd_elems,pack_fwd,stat_tiles,fwd} take the stem path for this descriptor
 bool rsp_stem_applicable(const rsp_conv3d_desc* d);
 int rsp_stem_tiles(const rsp_conv3d_desc* d);            // stat-partial tiles written by rsp_stem_fwd

@@ -701,23 +701,13 @@ int launch_w_vec(const WgradParams& p, bool va, bool vb, hipStream_t s) {
   return launch_w<BM, BN, WAVES_M, WAVES_N, false, false>(p, s);
 }
 
-bool wdesc_ok(const rsp_conv3d_desc* d) {
-  if (!d) return false;
-  if (d->N <= 0 || d->Cin <= 0 || d->Cout <= 0) return false;
-  if (d->kT <= 0 || d->kH <= 0 || d->kW <= 0 || d->kT * d->kH * d->kW > MAX_TAPS) return false;
-  if (d->sT <= 0 || d->sH <= 0 || d->sW <= 0 || d->pT < 0 || d->pH < 0 || d->pW < 0) return false;
-  if (d->Do != (d->Di + 2 * d->pT - d->kT) / d->sT + 1) return false;
-  if (d->Ho != (d->Hi + 2 * d->pH - d->kH) / d->sH + 1) return false;
-  if (d->Wo != (d->Wi + 2 * d->pW - d->kW) / d->sW + 1) return false;
-  if (d->Do <= 0 || d->Ho <= 0 || d->Wo <= 0) return false;
-  if (d->in_ld < d->Cin || d->out_ld < d->Cout) return false;
-  if ((long long)d->N * d->Do * d->Ho * d->Wo >= (1ll << 31)) return false;
-  return true;
-}
+bool wdesc_ok(const rsp_conv3d_desc* d) { return rsp_conv_desc_ok(d); }
 
 struct WPlan {
   int bm, bn, co_tiles, k_tiles, splitm, rows_per_split, Kld;
   size_t partial_bytes, colsum_bytes, rowgeom_bytes;
+  bool dma;      // the LDS-DMA kernels apply as far as the descriptor tells (16-byte rows of x and dy; wgrad_one adds the pointers and extents)
+  bool h16;      // ... on the 32-row tile's two-16-x-16-block instance (wgrad_h16)
 };
 
 WPlan wplan(const rsp_conv3d_desc* d) {
@@ -757,6 +747,8 @@ WPlan wplan(const rsp_conv3d_desc* d) {
   w.partial_bytes = rsp_align_up((size_t)w.splitm * d->Cout * w.Kld * sizeof(float), 256);
   w.colsum_bytes = rsp_align_up((size_t)rsp_cdiv(M, 1024) * d->Cout * sizeof(float), 256);
   w.rowgeom_bytes = rsp_align_up((size_t)M * sizeof(uint2), 256);
+  w.dma = d->Cout % 4 == 0 && d->out_ld % 4 == 0 && d->Cin % 4 == 0 && d->in_ld % 4 == 0 && d->kT <= 8 && d->kH <= 8 && d->kW <= 8;
+  w.h16 = w.bm == 32 && wgrad_h16(d->Cout);
   return w;
 }
 
@@ -771,10 +763,8 @@ const char* rsp_wgrad_kernel_name(const rsp_conv3d_desc* d0) {
   first.Cout = wgrad_segments(d0).width[0];     // a convolution run as several output-channel segments is named after the first
   const rsp_conv3d_desc* d = &first;
   const WPlan w = wplan(d);
-  const bool dma = d->Cout % 4 == 0 && d->out_ld % 4 == 0 && d->Cin % 4 == 0 && d->in_ld % 4 == 0 && d->kT <= 8 && d->kH <= 8 &&
-                   d->kW <= 8;
-  if (w.bm == 32) return dma ? (wgrad_h16(d->Cout) ? "wgrad_dma_h16_kernel" : "wgrad_dma_kernel<32, 128, 1, 4>") : "wgrad_kernel<32, 128, 1, 4, *>";
-  if (dma) return w.bm == 128 ? (w.bn == 128 ? "wgrad_dma_kernel<128, 128, 2, 2>" : "wgrad_dma_kernel<128, 64, 2, 2>")
+  if (w.bm == 32) return w.dma ? (w.h16 ? "wgrad_dma_h16_kernel" : "wgrad_dma_kernel<32, 128, 1, 4>") : "wgrad_kernel<32, 128, 1, 4, *>";
+  if (w.dma) return w.bm == 128 ? (w.bn == 128 ? "wgrad_dma_kernel<128, 128, 2, 2>" : "wgrad_dma_kernel<128, 64, 2, 2>")
                               : (w.bn == 128 ? "wgrad_dma_kernel<64, 128, 2, 2>" : "wgrad_dma_kernel<64, 64, 2, 2>");
   return w.bm == 128 ? (w.bn == 128 ? "wgrad_kernel<128, 128, 2, 2, *>" : "wgrad_kernel<128, 64, 2, 2, *>")
                      : (w.bn == 128 ? "wgrad_kernel<64, 128, 2, 2, *>" : "wgrad_kernel<64, 64, 2, 2, *>");
@@ -852,11 +842,9 @@ double rsp_wgrad_executed_fraction(const rsp_conv3d_desc* d0) {
     rsp_conv3d_desc seg = *d0;
     seg.Cout = g.width[i];
     const WPlan w = wplan(&seg);
-    const bool dma = seg.Cout % 4 == 0 && seg.out_ld % 4 == 0 && seg.Cin % 4 == 0 && seg.in_ld % 4 == 0 && seg.kT <= 8 && seg.kH <= 8 &&
-                     seg.kW <= 8;
     const WSkip k = wgrad_skip_plan(&seg, w);
     // (frame-granular: a 32-row chunk that straddles a live and a dead frame still runs)
-    const double f = (dma && k.skip_pad) ? 1.0 - (double)k.dead_frames / ((double)w.k_tiles * seg.Do) : 1.0;
+    const double f = (w.dma && k.skip_pad) ? 1.0 - (double)k.dead_frames / ((double)w.k_tiles * seg.Do) : 1.0;
     live += f * seg.Cout;
     tot += seg.Cout;
   }
@@ -999,7 +987,7 @@ int wgrad_one(const rsp_conv3d_desc* d, const float* x, const float* dy, float* 
   const unsigned long long dyb = (unsigned long long)p.M * d->out_ld * 4ull;
   p.x_bytes = (unsigned)xb;
   p.dy_bytes = (unsigned)dyb;
-  bool dma = va && vb && xb < (1ull << 32) && dyb < (1ull << 32) && d->kT <= 8 && d->kH <= 8 && d->kW <= 8 &&
+  bool dma = w.dma && va && vb && xb < (1ull << 32) && dyb < (1ull << 32) &&
              (unsigned long long)p.M * sizeof(uint2) < (1ull << 32);   // row-geometry table addressed with 32-bit offsets
   int rc;
   if (dma) {
@@ -1016,7 +1004,7 @@ int wgrad_one(const rsp_conv3d_desc* d, const float* x, const float* dy, float* 
     }
     p.rowgeom = g.out;
   }
-  if (dma && w.bm == 32) rc = wgrad_h16(p.Cout) ? launch_w_dma_h16(p, s) : launch_w_dma<32, 128, 1, 4>(p, s);
+  if (dma && w.bm == 32) rc = w.h16 ? launch_w_dma_h16(p, s) : launch_w_dma<32, 128, 1, 4>(p, s);
   else if (w.bm == 32) rc = launch_w_vec<32, 128, 1, 4>(p, va, vb, s);
   else if (dma && w.bm == 128 && w.bn == 128) rc = launch_w_dma<128, 128, 2, 2>(p, s);
   else if (dma && w.bm == 128) rc = launch_w_dma<128, 64, 2, 2>(p, s);

@@ -88,7 +88,8 @@ import functools
 @functools.lru_cache(maxsize=4096)
 def _conv_plan(lib_id, g: "ConvGeom", in_ld, out_ld):
     """ctypes descriptor + geometry-derived sizes of one conv application, built once per distinct geometry (the
-    per-launch host cost matters for the small-layer backbones: ~700-2500 launches per step)."""
+    per-launch host cost matters for the small-layer backbones: ~700-2500 launches per step).  Names and workspace sizes are read
+    off the plan the library's launch path executes (conv_igemm.hip plan_conv): one decision, not a second derivation."""
     lib = _lib.load()
     d = g.desc(in_ld=in_ld, out_ld=out_ld)
     ref = C.byref(d)

@@ -655,9 +655,10 @@ NAME_CASES = [
 
 @pytest.mark.parametrize("case", NAME_CASES, ids=lambda c: "x".join(map(str, c[:6])) + f"k{c[6]}s{c[7]}")
 def test_reported_kernel_name_is_the_kernel_that_ran(hip, case):
-    """rsp_conv3d_kernel_name (what bench.py labels its roofline block and the traffic lookup with) re-derives the dispatch
-    decision; the launchers record the instance they actually started (rsp_last_conv_kernel).  The two must agree for forward,
-    dgrad and wgrad of every dispatch family."""
+    """rsp_conv3d_kernel_name (what bench.py labels its roofline block and the traffic lookup with) formats the first launch of the
+    plan the launch path executes (conv_igemm.hip plan_conv / plan_multi, conv_wgrad.hip wplan); the launchers record the instance
+    they actually started (rsp_last_conv_kernel).  The two must agree for forward, dgrad and wgrad of every dispatch family: plan
+    and launch agree by construction, and this checks it on the GPU."""
     import ctypes as C
     N, D, H, W, cin, cout, k, s, p = case
     g = ConvGeom(N, D, H, W, cin, cout, k, s, p)
