@@ -258,6 +258,21 @@ int rsp_bn_act_pool_bwd_g(const rsp_pool3d_desc* d, const float* y, const float*
                           float* dres, float* dgamma, float* dbeta, int32_t c_valid, const float* gate, const float* dmean,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* Eval-mode counterpart of rsp_bn_act_pool_bwd_v — BatchNorm on its running statistics — in ONE pass over y and dout:
+ *   dz = gradient at the BatchNorm output after pool routing + ReLU mask, recomputed from y with the forward's tie rule
+ *   dy = scale*dz (0 on the padding channels [c_valid, C)); d(residual) = dz (if dres != NULL)
+ *   dgamma = sum(dz*xhat), dbeta = sum(dz), xhat = (y - mean')*invstd          (both nullable, c_valid entries)
+ * scale_shift [2][C] is what the forward applied; mean_invstd [2][C] holds mean' = running_mean - conv_bias and
+ * rsqrt(running_var + eps) and is read only when a parameter gradient is asked for.  With dgamma == dbeta == NULL no sums are
+ * formed and neither mean_invstd nor the workspace is touched (frozen affine parameters).  Otherwise every workgroup writes its
+ * partial sums to the workspace and one small launch adds them in a fixed order: no atomics, bit-identical run to run.  Same
+ * geometry conventions as rsp_bn_act_pool_bwd_v (disjoint windows of any size, separate pitches for y / dout / residual). */
+size_t rsp_bn_eval_bwd_workspace(const rsp_pool3d_desc* d);
+int rsp_bn_eval_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
+                             const float* mean_invstd, const float* scale_shift, int relu, float* dy, float* dres,
+                             float* dgamma, float* dbeta, int32_t c_valid, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
 /* Stand-alone MaxPool3d, any window/stride/padding (models/resnet.py:139, models/s3dg.py:90,107-119).
  * argmax (nullable in forward when no backward is needed): [N,Do,Ho,Wo,C] int32, linear input position per sample. */
 int rsp_maxpool3d_fwd(const rsp_pool3d_desc* d, const float* x, float* out, int32_t* argmax, void* stream);

@@ -110,6 +110,8 @@ SIGNATURES = {
     "rsp_bn_act_pool_bwd": (C.c_int, [_PP, _p, _p, _p, _p, _p, _p, C.c_int, _p, _p, _p, _p, _p, _sz, _p]),
     "rsp_bn_act_pool_bwd_v": (C.c_int, [_PP, _p, _p, _p, _p, _p, _p, C.c_int, _p, _p, _p, _p, _i32, _p, _sz, _p]),
     "rsp_bn_act_pool_bwd_g": (C.c_int, [_PP, _p, _p, _p, _p, _p, _p, C.c_int, _p, _p, _p, _p, _i32, _p, _p, _p, _sz, _p]),
+    "rsp_bn_eval_bwd_workspace": (_sz, [_PP]),
+    "rsp_bn_eval_act_pool_bwd": (C.c_int, [_PP, _p, _p, _p, _p, _p, C.c_int, _p, _p, _p, _p, _i32, _p, _sz, _p]),
     "rsp_maxpool3d_fwd": (C.c_int, [_PP, _p, _p, _p, _p]),
     "rsp_maxpool3d_bwd": (C.c_int, [_PP, _p, _p, _p, _p]),
     "rsp_gate_fwd_workspace": (_sz, [_i32, _i32, _i32]),

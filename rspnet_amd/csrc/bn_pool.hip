@@ -892,6 +892,251 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BwdParams p
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// backward, eval mode (BatchNorm on its running statistics): ONE pass
+// ------------------------------------------------------------------------------------------------------------------
+// Without the batch mean nothing couples the positions of a channel: dy = scale * dz is local, so the pass that recomputes the
+// activation's mask / arg-max from y also writes dy (and dres) and, when parameter gradients are wanted, accumulates the
+// per-channel sums of dz and dz * xhat.  y and dout are read once, whatever the window; a small finalize launch adds the
+// per-workgroup partials in a fixed order (fin_sum_partials).  Three tensors moved where the train-mode pair moves five.
+struct EvalBwdParams {
+  rsp_pool3d_desc d;
+  const float* __restrict__ y;
+  const float* __restrict__ res;   // nullable
+  const float* __restrict__ dout;  // [N,Do,Ho,Wo,C] pitch out_ld
+  const float* __restrict__ mi;    // mean' = running_mean - conv_bias, invstd [2][C]  (read only when partials are written)
+  const float* __restrict__ ss;    // scale, shift [2][C]: what the forward used
+  float* __restrict__ partial;     // [gridDim.x][C][2] (sum dz, sum dz*xhat)          (SUMS only)
+  float* __restrict__ dy;
+  float* __restrict__ dres;        // nullable
+  int relu;
+  int cg;
+  int Cv;            // channels [Cv, C) are zero padding: dy = 0 there
+  int cgc, ppi;      // thread layout (see Layout)
+  long long npos;    // what the grid walks: output positions (modes 1-3) or windows including the clipped last ones (mode 0)
+  int De, He, We;    // mode 0: windows per axis including a clipped last one = ceil(Di / sT) ...
+  FastDiv dcgc, dW, dH, dD;      // of (Wo, Ho, Do) in modes 2 / 3, of (We, He, De) in mode 0
+};
+
+// MODE as in bn_act_pool_fwd_kernel: 1 unit windows (streaming), 2 / 3 windows of 4 / 8 positions that tile the input exactly,
+// 0 any other disjoint window (more than 8 positions, or an input the windows do not tile: the positions behind the last whole
+// window belong to no output and get dy = dres = 0 from the thread that owns their clipped window — no separate zero fill).
+// SUMS = false is the frozen-affine form: no statistics loaded, nothing accumulated, no partials written; dy / dres are computed
+// by the same expressions in the same order either way.
+template <int VEC, int MODE, bool SUMS>
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const EvalBwdParams p) {
+  const rsp_pool3d_desc& d = p.d;
+  const int cg0 = blockIdx.y * 256;
+  const int cgc = min(p.cg - cg0, 256);
+  const int t = threadIdx.x;
+  const int pl = fastdiv(t, p.dcgc);
+  const int cl = t - pl * p.cgc;
+  const bool active = pl < p.ppi && cl < cgc;
+  const int c = (cg0 + cl) * VEC;
+  float s1[VEC], s2[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) s1[e] = s2[e] = 0.f;
+  if (active) {
+    float sc[VEC], sh[VEC], scd[VEC], mean[VEC], invstd[VEC];
+    load_vec<VEC>(p.ss + c, sc);
+    load_vec<VEC>(p.ss + d.C + c, sh);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) { scd[e] = c + e < p.Cv ? sc[e] : 0.f; mean[e] = 0.f; invstd[e] = 0.f; }
+    if constexpr (SUMS) {
+      load_vec<VEC>(p.mi + c, mean);
+      load_vec<VEC>(p.mi + d.C + c, invstd);
+    }
+    long long o = (long long)blockIdx.x * p.ppi + pl;
+    const long long stride = (long long)gridDim.x * p.ppi;
+    if constexpr (MODE == 1) {
+      // four consecutive position groups per trip, every load of a trip issued before the first use (see bn_act_pool_fwd_kernel)
+      const long long step = p.ppi;
+      o = (long long)blockIdx.x * p.ppi * 4 + pl;
+      for (; o + 3 * step < p.npos; o += stride * 4) {
+        float yv[4][VEC], r[4][VEC], g[4][VEC];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          load_vec<VEC>(p.y + (o + u * step) * d.in_ld + c, yv[u]);
+          if (p.res) load_vec<VEC>(p.res + (o + u * step) * d.res_ld + c, r[u]);
+          load_vec<VEC>(p.dout + (o + u * step) * d.out_ld + c, g[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          float ov[VEC], dz[VEC];
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) {
+            float z = fmaf(yv[u][e], sc[e], sh[e]);
+            if (p.res) z += r[u][e];
+            dz[e] = (p.relu && !(z > 0.f)) ? 0.f : g[u][e];
+            ov[e] = scd[e] * dz[e];
+            if constexpr (SUMS) {
+              s1[e] += dz[e];
+              s2[e] = fmaf(dz[e], (yv[u][e] - mean[e]) * invstd[e], s2[e]);
+            }
+          }
+          store_vec<VEC>(p.dy + (o + u * step) * d.in_ld + c, ov);
+          if (p.dres) store_vec<VEC>(p.dres + (o + u * step) * d.res_ld + c, dz);
+        }
+      }
+      for (int u = 0; u < 4 && o < p.npos; ++u, o += step) {      // the last, partial group of four
+        float yv[VEC], z[VEC], g[VEC], ov[VEC], dz[VEC];
+        load_vec<VEC>(p.y + o * d.in_ld + c, yv);
+        if (p.res) load_vec<VEC>(p.res + o * d.res_ld + c, z);
+        load_vec<VEC>(p.dout + o * d.out_ld + c, g);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+          const float zz = fmaf(yv[e], sc[e], sh[e]) + (p.res ? z[e] : 0.f);
+          dz[e] = (p.relu && !(zz > 0.f)) ? 0.f : g[e];
+          ov[e] = scd[e] * dz[e];
+          if constexpr (SUMS) {
+            s1[e] += dz[e];
+            s2[e] = fmaf(dz[e], (yv[e] - mean[e]) * invstd[e], s2[e]);
+          }
+        }
+        store_vec<VEC>(p.dy + o * d.in_ld + c, ov);
+        if (p.dres) store_vec<VEC>(p.dres + o * d.res_ld + c, dz);
+      }
+    } else if constexpr (MODE == 2 || MODE == 3) {
+      // whole windows of 4 or 8 positions: loads first, then the arg-max (first maximum in scan order), then the stores
+      constexpr int NW = MODE == 2 ? 4 : 8;
+      long long off[NW];
+      window_offsets<NW>(d, off);
+      for (; o < p.npos; o += stride) {
+        const int op = (int)o;
+        const int q1 = fastdiv(op, p.dW), ow = op - q1 * d.Wo;
+        const int q2 = fastdiv(q1, p.dH), oh = q1 - q2 * d.Ho;
+        const int n = fastdiv(q2, p.dD), od = q2 - n * d.Do;
+        const long long base = (((long long)n * d.Di + od * d.sT) * d.Hi + oh * d.sH) * d.Wi + ow * d.sW;
+        float yv[NW][VEC], r[NW][VEC], g[VEC], best[VEC], by[VEC];
+        int bi[VEC];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+          load_vec<VEC>(p.y + (base + off[w]) * d.in_ld + c, yv[w]);
+          if (p.res) load_vec<VEC>(p.res + (base + off[w]) * d.res_ld + c, r[w]);
+        }
+        load_vec<VEC>(p.dout + o * d.out_ld + c, g);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) { best[e] = -INFINITY; bi[e] = 0; by[e] = 0.f; }
+#pragma unroll
+        for (int w = 0; w < NW; ++w)
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) {
+            float z = fmaf(yv[w][e], sc[e], sh[e]);
+            if (p.res) z += r[w][e];
+            const float v = p.relu ? fmaxf(z, 0.f) : z;
+            if (v > best[e]) { best[e] = v; bi[e] = w; by[e] = yv[w][e]; }
+          }
+        float dzo[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+          dzo[e] = (p.relu && !(best[e] > 0.f)) ? 0.f : g[e];
+          if constexpr (SUMS) {
+            s1[e] += dzo[e];
+            s2[e] = fmaf(dzo[e], (by[e] - mean[e]) * invstd[e], s2[e]);
+          }
+        }
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+          float ov[VEC], dz[VEC];
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) {
+            dz[e] = bi[e] == w ? dzo[e] : 0.f;
+            ov[e] = scd[e] * dz[e];
+          }
+          store_vec<VEC>(p.dy + (base + off[w]) * d.in_ld + c, ov);
+          if (p.dres) store_vec<VEC>(p.dres + (base + off[w]) * d.res_ld + c, dz);
+        }
+      }
+    } else {
+      for (; o < p.npos; o += stride) {
+        const int op = (int)o;
+        const int q1 = fastdiv(op, p.dW), ow = op - q1 * p.We;
+        const int q2 = fastdiv(q1, p.dH), oh = q1 - q2 * p.He;
+        const int n = fastdiv(q2, p.dD), od = q2 - n * p.De;
+        const bool whole = od < d.Do && oh < d.Ho && ow < d.Wo;      // else: a clipped window behind the last output
+        const int t0 = od * d.sT, h0 = oh * d.sH, w0 = ow * d.sW;
+        const int nt = min(d.kT, d.Di - t0), nh = min(d.kH, d.Hi - h0), nw = min(d.kW, d.Wi - w0);
+        float best[VEC], by[VEC], dzo[VEC];
+        int bi[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) { best[e] = -INFINITY; bi[e] = 0; by[e] = 0.f; dzo[e] = 0.f; }
+        if (whole) {
+          for (int kt = 0; kt < nt; ++kt)
+            for (int kh = 0; kh < nh; ++kh)
+              for (int kw = 0; kw < nw; ++kw) {
+                const long long pos = (((long long)n * d.Di + t0 + kt) * d.Hi + h0 + kh) * d.Wi + w0 + kw;
+                float yv[VEC], r[VEC];
+                load_vec<VEC>(p.y + pos * d.in_ld + c, yv);
+                if (p.res) load_vec<VEC>(p.res + pos * d.res_ld + c, r);
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                  float z = fmaf(yv[e], sc[e], sh[e]);
+                  if (p.res) z += r[e];
+                  const float v = p.relu ? fmaxf(z, 0.f) : z;
+                  if (v > best[e]) { best[e] = v; bi[e] = (kt * d.kH + kh) * d.kW + kw; by[e] = yv[e]; }
+                }
+              }
+          const long long oo = (((long long)n * d.Do + od) * d.Ho + oh) * d.Wo + ow;
+          float g[VEC];
+          load_vec<VEC>(p.dout + oo * d.out_ld + c, g);
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) {
+            dzo[e] = (p.relu && !(best[e] > 0.f)) ? 0.f : g[e];
+            if constexpr (SUMS) {
+              s1[e] += dzo[e];
+              s2[e] = fmaf(dzo[e], (by[e] - mean[e]) * invstd[e], s2[e]);
+            }
+          }
+        }
+        for (int kt = 0; kt < nt; ++kt)
+          for (int kh = 0; kh < nh; ++kh)
+            for (int kw = 0; kw < nw; ++kw) {
+              const long long pos = (((long long)n * d.Di + t0 + kt) * d.Hi + h0 + kh) * d.Wi + w0 + kw;
+              const int w = (kt * d.kH + kh) * d.kW + kw;
+              float ov[VEC], dz[VEC];
+#pragma unroll
+              for (int e = 0; e < VEC; ++e) {
+                dz[e] = (whole && bi[e] == w) ? dzo[e] : 0.f;
+                ov[e] = scd[e] * dz[e];
+              }
+              store_vec<VEC>(p.dy + pos * d.in_ld + c, ov);
+              if (p.dres) store_vec<VEC>(p.dres + pos * d.res_ld + c, dz);
+            }
+      }
+    }
+  }
+  if constexpr (SUMS) {
+    // per-workgroup partials, position lanes added in index order (as bn_bwd_reduce_kernel)
+    __shared__ float red[256][2 * VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) { red[t][e] = s1[e]; red[t][VEC + e] = s2[e]; }
+    __syncthreads();
+    if (t < cgc) {
+      float a1[VEC], a2[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) a1[e] = a2[e] = 0.f;
+      for (int l = 0; l < p.ppi; ++l)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) { a1[e] += red[l * p.cgc + t][e]; a2[e] += red[l * p.cgc + t][VEC + e]; }
+      float* o = p.partial + ((long long)blockIdx.x * d.C + (cg0 + t) * VEC) * 2;
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) { o[2 * e] = a1[e]; o[2 * e + 1] = a2[e]; }
+    }
+  }
+}
+
+// dbeta[c] = sum dz, dgamma[c] = sum dz*xhat over the per-workgroup partials, in double and in a fixed order
+__global__ __launch_bounds__(1024) void bn_eval_bwd_finalize_kernel(const float* __restrict__ partial, int nblocks, int C, int Cv,
+                                                                    float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int c = blockIdx.x * FIN_CH + (threadIdx.x & (FIN_CH - 1));
+  double a, b;
+  if (!fin_sum_partials(partial, nblocks, C, C, a, b)) return;
+  if (dbeta && c < Cv) dbeta[c] = (float)a;
+  if (dgamma && c < Cv) dgamma[c] = (float)b;
+}
+
+constexpr int EVAL_BWD_MAX_BLOCKS = 4096;
+
 bool pool_ok(const rsp_pool3d_desc* d, bool need_disjoint) {
   if (!d) return false;
   if (d->N <= 0 || d->C <= 0 || d->kT <= 0 || d->kH <= 0 || d->kW <= 0) return false;
@@ -1126,6 +1371,90 @@ int rsp_bn_act_pool_bwd_g(const rsp_pool3d_desc* d, const float* y, const float*
   if (vec) hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(grid_for(total)), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(grid_for(total)), dim3(256), 0, s, p);
   return rsp_check_launch("bn_bwd_apply_kernel");
+}
+
+// ---- eval-mode backward (one pass) ---------------------------------------------------------------------------------
+// Mode of bn_eval_bwd_kernel: the 4 / 8-position bodies own whole windows, so they need the windows to tile the input exactly.
+static int eval_bwd_mode(const rsp_pool3d_desc* d) {
+  const int m = bn_mode(d, false);
+  if (m == 1) return 1;
+  const bool exact = d->Di % d->sT == 0 && d->Hi % d->sH == 0 && d->Wi % d->sW == 0;
+  return exact ? m : 0;
+}
+
+// positions the grid walks (see EvalBwdParams::npos)
+static long long eval_bwd_npos(const rsp_pool3d_desc* d, int mode) {
+  if (mode != 0) return (long long)d->N * d->Do * d->Ho * d->Wo;
+  return (long long)d->N * rsp_cdiv(d->Di, d->sT) * rsp_cdiv(d->Hi, d->sH) * rsp_cdiv(d->Wi, d->sW);
+}
+
+size_t rsp_bn_eval_bwd_workspace(const rsp_pool3d_desc* d) {
+  if (!pool_ok(d, true)) return 0;
+  const long long npos = eval_bwd_npos(d, eval_bwd_mode(d));
+  const long long rows = npos < EVAL_BWD_MAX_BLOCKS ? npos : EVAL_BWD_MAX_BLOCKS;      // never more workgroups than positions
+  return (size_t)rows * d->C * 2 * sizeof(float);
+}
+
+#define RSP_BN_EVAL_LAUNCH_S(V, M, grid, stream, p)                                                                       \
+  do {                                                                                                                    \
+    if (sums) hipLaunchKernelGGL((bn_eval_bwd_kernel<V, M, true>), grid, dim3(256), 0, stream, p);                        \
+    else hipLaunchKernelGGL((bn_eval_bwd_kernel<V, M, false>), grid, dim3(256), 0, stream, p);                            \
+  } while (0)
+#define RSP_BN_EVAL_LAUNCH_V(V, mode, grid, stream, p)                                                                    \
+  do {                                                                                                                    \
+    switch (mode) {                                                                                                       \
+      case 1: RSP_BN_EVAL_LAUNCH_S(V, 1, grid, stream, p); break;                                                         \
+      case 2: RSP_BN_EVAL_LAUNCH_S(V, 2, grid, stream, p); break;                                                         \
+      case 3: RSP_BN_EVAL_LAUNCH_S(V, 3, grid, stream, p); break;                                                         \
+      default: RSP_BN_EVAL_LAUNCH_S(V, 0, grid, stream, p); break;                                                        \
+    }                                                                                                                     \
+  } while (0)
+
+int rsp_bn_eval_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
+                             const float* mean_invstd, const float* scale_shift, int relu, float* dy, float* dres,
+                             float* dgamma, float* dbeta, int32_t c_valid, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  RSP_REQUIRE(pool_ok(d, true), "rsp_bn_eval_act_pool_bwd: needs disjoint windows (kernel == stride, no padding)");
+  RSP_REQUIRE(c_valid > 0 && c_valid <= d->C, "rsp_bn_eval_act_pool_bwd: bad valid channel count");
+  RSP_REQUIRE(y && dout && scale_shift && dy, "rsp_bn_eval_act_pool_bwd: null pointer");
+  RSP_REQUIRE(!dres || residual, "rsp_bn_eval_act_pool_bwd: dres without a residual");
+  RSP_REQUIRE(d->res_ld >= d->C || !residual, "rsp_bn_eval_act_pool_bwd: bad residual pitch");
+  const bool sums = dgamma || dbeta;
+  RSP_REQUIRE(!sums || (mean_invstd && workspace), "rsp_bn_eval_act_pool_bwd: parameter gradients need mean_invstd and a workspace");
+  if (sums && workspace_bytes < rsp_bn_eval_bwd_workspace(d)) {
+    rsp_set_error("rsp_bn_eval_act_pool_bwd: workspace too small");
+    return RSP_EWORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  EvalBwdParams p;
+  memset(&p, 0, sizeof p);
+  p.d = *d; p.y = y; p.res = residual; p.dout = dout; p.mi = mean_invstd; p.ss = scale_shift;
+  p.partial = sums ? reinterpret_cast<float*>(workspace) : nullptr;
+  p.dy = dy; p.dres = dres; p.relu = relu; p.Cv = c_valid;
+  const bool vec = d->C % 4 == 0 && d->in_ld % 4 == 0 && d->out_ld % 4 == 0 && rsp_aligned16(y) && rsp_aligned16(dout) &&
+                   rsp_aligned16(dy) && rsp_aligned16(scale_shift) && (!sums || rsp_aligned16(mean_invstd)) &&
+                   (!residual || (d->res_ld % 4 == 0 && rsp_aligned16(residual) && (!dres || rsp_aligned16(dres))));
+  p.cg = vec ? d->C / 4 : d->C;
+  const int mode = eval_bwd_mode(d);
+  p.npos = eval_bwd_npos(d, mode);
+  RSP_REQUIRE(p.npos < (1ll << 31), "rsp_bn_eval_act_pool_bwd: more than 2^31 - 1 positions");
+  p.cgc = p.cg < 256 ? p.cg : 256;
+  p.ppi = 256 / p.cgc;
+  p.dcgc = fastdiv_make(p.cgc);
+  p.De = rsp_cdiv(d->Di, d->sT); p.He = rsp_cdiv(d->Hi, d->sH); p.We = rsp_cdiv(d->Wi, d->sW);
+  if (mode == 0) { p.dW = fastdiv_make(p.We); p.dH = fastdiv_make(p.He); p.dD = fastdiv_make(p.De); }
+  else { p.dW = fastdiv_make(d->Wo); p.dH = fastdiv_make(d->Ho); p.dD = fastdiv_make(d->Do); }
+  // >= 16 positions per thread: the partials stay a few per cent of the tensors' bytes even at 832 channels
+  long long b = (p.npos + (long long)p.ppi * 16 - 1) / ((long long)p.ppi * 16);
+  b = b > EVAL_BWD_MAX_BLOCKS ? EVAL_BWD_MAX_BLOCKS : (b < 1 ? 1 : b);
+  const dim3 grid((unsigned)b, (unsigned)rsp_cdiv(p.cg, 256));
+  if (vec) RSP_BN_EVAL_LAUNCH_V(4, mode, grid, s, p);
+  else RSP_BN_EVAL_LAUNCH_V(1, mode, grid, s, p);
+  int rc = rsp_check_launch("bn_eval_bwd_kernel");
+  if (rc != RSP_OK || !sums) return rc;
+  hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(rsp_cdiv(d->C, FIN_CH)), dim3(1024), 0, s, p.partial, (int)b, d->C, c_valid,
+                     dgamma, dbeta);
+  return rsp_check_launch("bn_eval_bwd_finalize_kernel");
 }
 
 }  // extern "C"

@@ -122,6 +122,7 @@ class _Saved:
     cg: ConvGeom
     pg: PoolGeom
     res: Optional[torch.Tensor] = None
+    eval_mode: bool = False                        # BatchNorm ran on its running statistics: mi is _eval_mean_invstd's
 
 
 @dataclass
@@ -523,13 +524,25 @@ def _eval_scale_shift(bn, bias) -> torch.Tensor:
     return torch.stack([scale, shift]).contiguous()
 
 
+def _eval_mean_invstd(bn, bias) -> torch.Tensor:
+    """What the eval-mode backward needs next to (scale, shift): xhat = (conv - mean') * invstd with mean' = running_mean - b
+    (the saved convolution output carries no bias) and invstd = 1 / sqrt(running_var + eps)."""
+    mean = bn.running_mean if bias is None else bn.running_mean - bias.data
+    return torch.stack([mean, torch.rsqrt(bn.running_var + float(bn.eps))]).contiguous()
+
+
+EVAL_BACKWARD_MISSING = ("backward through an eval-mode backbone (BatchNorm on running statistics) is not implemented: "
+                         "freeze the backbone (only_train_fc) or call model.train()")
+
+
 def run_forward(plan: Plan, x: torch.Tensor, packed: PackedWeights, keep: bool, training: bool = True,
                 deferred: Optional[Dict[int, torch.Tensor]] = None) -> Tuple[torch.Tensor, Optional[ForwardCtx]]:
     """Execute `plan` on x (N,D,H,W,C).  keep=True records what backward needs.  training=True: batch-statistics BN (the
     pretext step never runs anything else: pretrain.py:225); training=False: running-statistics BN for the fine-tune /
-    validation forward (finetune.py:333-345), no backward."""
+    validation forward (finetune.py:333-345) and for fine-tuning with frozen BatchNorm (keep=True: the backward then runs
+    bn_eval_act_pool_bwd per ConvBN; no virtual stem, no grouped convolutions, no gate fusion in this mode, so Gate and Pool nodes
+    keep their ordinary saved state)."""
     be = _ops.backend()
-    assert training or not keep, "eval-mode forward keeps nothing for backward"
 
     def finalize(bn, stats, rows, bias_d):
         # deferred: {id(BatchNorm module): [2][C] buffer} — this pass reports its batch moments there and leaves the running
@@ -622,9 +635,11 @@ def run_forward(plan: Plan, x: torch.Tensor, packed: PackedWeights, keep: bool, 
         else:
             y, _ = be.conv_fwd(cg, xin, packed.get(node, cg), None, False)     # bias folded into the shift
             ss = _eval_scale_shift(bn, bias)
-            mi = None
+            mi = _eval_mean_invstd(bn, bias) if keep else None
             if Cp != Cout:
                 ss = torch.cat([ss, torch.zeros((2, Cp - Cout), dtype=ss.dtype, device=ss.device)], dim=1).contiguous()
+                if mi is not None:
+                    mi = torch.cat([mi, torch.zeros((2, Cp - Cout), dtype=mi.dtype, device=mi.device)], dim=1).contiguous()
         do, ho, wo = cg.out_dims
         if gated is not None:
             # BatchNorm-apply + self-gating (+ the max-pool behind a front-end unit, when nothing is kept for a backward) in two
@@ -663,7 +678,7 @@ def run_forward(plan: Plan, x: torch.Tensor, packed: PackedWeights, keep: bool, 
             return
         pg, res = bn_apply(node, y, ss, cg.Cout, N, do, ho, wo, xin, key)
         if keep:
-            ctx.saved[key] = _Saved(xin, y, mi, ss, cg, pg, res)
+            ctx.saved[key] = _Saved(xin, y, mi, ss, cg, pg, res, eval_mode=not training)
 
     def convbn_group(node, ni):
         """One GEMM over the members' concatenated filters (see ConvBNGroup); falls back to member-by-member execution."""
@@ -817,14 +832,37 @@ def run_backward_iter(plan: Plan, ctx: ForwardCtx, dfeat: torch.Tensor, grad_of,
             dres = None
             if after_param_grads is not None:
                 after_param_grads(gi, branches.grads_ready)
+        elif sv.eval_mode:
+            return convbn_eval_bwd(node, sv, ni)
         else:
             dout = _view(dslots[node.into[0]], node.into, sv.cg.Cout) if node.into is not None else dslots.pop(node.dst)
             dy, dres = be.bn_act_pool_bwd(sv.pg, sv.y, sv.res, dout, bn.weight.data, sv.mi, sv.ss, node.relu,
                                           node.residual is not None, grad_of(bn.weight), grad_of(bn.bias))
+        convbn_tail(node, sv, ni, dy, dres, True)
+
+    def convbn_eval_bwd(node, sv, ni):
+        """ConvBN whose forward ran BatchNorm on its running statistics: dy = scale * dz in one pass (bn_eval_act_pool_bwd)."""
+        if not hasattr(be, "bn_eval_act_pool_bwd"):
+            raise RuntimeError(EVAL_BACKWARD_MISSING)
+        bn = node.bn
+        dout = _view(dslots[node.into[0]], node.into, sv.cg.Cout) if node.into is not None else dslots.pop(node.dst)
+        bias = getattr(node.conv, "bias", None)
+        gbias = grad_of(bias) if bias is not None else None
+        dgamma, dbeta = grad_of(bn.weight), grad_of(bn.bias)
+        # the bias gradient comes from the dbeta sums — also with frozen affine parameters: the sums then land in a scratch vector
+        sums = dbeta if (dbeta is not None or gbias is None) else torch.empty_like(bn.bias.data)
+        dy, dres = be.bn_eval_act_pool_bwd(sv.pg, sv.y, sv.res, dout, sv.mi, sv.ss, node.relu, node.residual is not None, dgamma, sums)
+        if gbias is not None:
+            # out = (conv + b) * scale + shift0: d/db = scale * sum dz.  (Train-mode BatchNorm subtracts the batch mean and cancels
+            # it; running statistics do not.)
+            torch.mul(sv.ss[0][:gbias.shape[0]], sums, out=gbias)
+        convbn_tail(node, sv, ni, dy, dres, False)
+
+    def convbn_tail(node, sv, ni, dy, dres, zero_bias):
         if node.residual is not None:
             add_grad(node.residual, dres)
         bias = getattr(node.conv, "bias", None)
-        if bias is not None:
+        if bias is not None and zero_bias:
             gb = grad_of(bias)
             if gb is not None:
                 # A conv bias in front of train-mode BatchNorm has an identically-zero gradient (BN subtracts the

@@ -309,7 +309,10 @@ class Engine:
                                       "use model_type 'multitask'")
         if model_type != "multitask":
             raise ValueError(f'Unrecognized model_type "{model_type}"')
-        self.model = ModelFactory(cfg).build_multitask_wrapper(local_rank)
+        self.model = ModelFactory(cfg).build_multitask_wrapper(local_rank)      # (honours only_train_fc, freeze_bn, freeze_bn_affine)
+        if getattr(self.model.module, "bn_frozen", False):
+            logger.info("BatchNorm frozen: the encoder stays on its running statistics while it trains (freeze_bn)%s",
+                        "; BatchNorm weight / bias frozen too (freeze_bn_affine)" if _get(cfg, "freeze_bn_affine", False) else "")
         self.n_crop = int(_need(cfg, "temporal_transforms.validate.final_n_crop" if final_validate
                                 else "temporal_transforms.validate.n_crop"))
         self.criterion = FusedCrossEntropy()

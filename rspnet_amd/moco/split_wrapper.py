@@ -10,7 +10,8 @@ pool+linear+normalize arithmetic is one HIP kernel (rsp_head_fwd); the other typ
 finetune=True (split_wrapper.py:104-106,131-135, built by models/__init__.py:125-143) is the downstream
 classifier: backbone -> AdaptiveAvgPool3d(1) -> Linear(feat, num_classes).  Its forward is a regular autograd node
 (`_FinetuneFn`) over the module's parameters, so `nn.CrossEntropyLoss`, any torch optimizer and DistributedDataParallel
-work on it exactly as finetune.py uses them; `model.eval()` switches BatchNorm to its running statistics.
+work on it exactly as finetune.py uses them; `model.eval()` switches BatchNorm to its running statistics — forward and,
+with trainable backbone parameters, backward (fine-tuning with frozen BatchNorm).
 """
 from typing import Callable
 
@@ -251,11 +252,12 @@ class _FinetuneFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module: MultiTaskWrapper, grad_on: bool, x: Tensor, *params):
         be = _ops.backend()
-        training = module.encoder.training                 # BatchNorm mode (only_train_fc keeps the backbone in eval mode)
+        training = module.encoder.training                 # BatchNorm mode (only_train_fc / freeze_bn keep the backbone in eval mode)
         names = [n for n, _ in module.named_parameters()]
         backbone_grad = grad_on and any(need for n, need in zip(names, ctx.needs_input_grad[3:]) if n.startswith("encoder."))
-        keep = training and backbone_grad
+        keep = backbone_grad                               # eval mode too: frozen BatchNorm (engine.convbn_eval_bwd)
         ctx.backbone_grad = backbone_grad
+        ctx.bn_training = training
         # weights may have been stepped by any optimizer since the last call: re-pack when their version counters moved
         ver = sum(p._version for p in params)
         if ver != getattr(module, "_packed_version", None):
@@ -279,7 +281,16 @@ class _FinetuneFn(torch.autograd.Function):
         module, params = ctx.module, ctx.params
         grads = {}
 
+        # frozen BatchNorm with frozen affine parameters (ModelFactory's freeze_bn_affine): no buffer, and the eval-mode backward
+        # forms no per-channel sums for them
+        skip = set()
+        if not ctx.bn_training:
+            skip = {id(p) for m in module.encoder.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)
+                    for p in (m.weight, m.bias) if p is not None and not p.requires_grad}
+
         def grad_of(p):
+            if id(p) in skip:
+                return None
             g = torch.empty_like(p)
             grads[id(p)] = g
             return g
@@ -287,9 +298,6 @@ class _FinetuneFn(torch.autograd.Function):
         pooled, logits = ctx.head
         dpooled = be.linear_bwd(pooled, logits, dlogits.contiguous(), module.fc.weight.data, False, grad_of(module.fc.weight),
                                 grad_of(module.fc.bias))
-        if ctx.ectx is None and ctx.backbone_grad:
-            raise RuntimeError("backward through an eval-mode backbone (BatchNorm on running statistics) is not implemented: "
-                               "freeze the backbone (only_train_fc) or call model.train()")
         if ctx.ectx is not None:                          # `only_train_fc` (models/__init__.py:82-104) stops at the classifier
             dfeat = be.spatial_mean_bwd(dpooled, ctx.feat_shape)
             run_backward(module.plan(), ctx.ectx, dfeat, grad_of)

@@ -25,7 +25,8 @@ def get_model_class(**kwargs) -> Callable[[int], nn.Module]:
 
 class ModelFactory:
     """Downstream (fine-tune) model factory — same entry points as /root/reference/models/__init__.py:76-143.
-    ``cfg`` is the resolved config (dict or pyhocon ConfigTree): keys ``model.arch``, ``dataset.num_classes``, ``only_train_fc``."""
+    ``cfg`` is the resolved config (dict or pyhocon ConfigTree): keys ``model.arch``, ``dataset.num_classes``, ``only_train_fc``
+    and — this project's own, the reference has no such switch — ``freeze_bn`` / ``freeze_bn_affine``."""
 
     def __init__(self, cfg):
         self.cfg = cfg
@@ -39,7 +40,11 @@ class ModelFactory:
         return node
 
     def _post_process_model(self, model: nn.Module):
-        """``only_train_fc``: freeze everything but the classifier and keep the backbone in eval mode (:82-104)."""
+        """``only_train_fc``: freeze everything but the classifier and keep the backbone in eval mode (:82-104).
+        ``freeze_bn`` (default false): fine-tune with frozen BatchNorm — ``train()`` keeps the encoder in eval mode (running
+        statistics, buffers never move) and lets the classifier follow ``mode``; ``requires_grad`` is left alone, so every
+        backbone parameter still trains.  With ``freeze_bn_affine`` (default false) the encoder's BatchNorm weight / bias are
+        frozen as well.  ``only_train_fc`` wins if both are set."""
         if self._get("only_train_fc", False):
             for param in model.parameters():
                 param.requires_grad = False
@@ -55,6 +60,25 @@ class ModelFactory:
                 fc_module.train(mode)
 
             model.train = override_train
+        elif self._get("freeze_bn", False):
+            encoder = getattr(model, "encoder", None)
+            if encoder is None:
+                raise Exception('"freeze_bn" specified, but the model has no encoder (use the multitask wrapper)')
+            if self._get("freeze_bn_affine", False):
+                for mod in encoder.modules():
+                    if isinstance(mod, nn.modules.batchnorm._BatchNorm):
+                        for param in (mod.weight, mod.bias):
+                            if param is not None:
+                                param.requires_grad = False
+            orig_train_bn = model.train
+
+            def override_train_bn(mode=True):
+                orig_train_bn(mode)
+                encoder.eval()
+                return model
+
+            model.train = override_train_bn
+            model.bn_frozen = True
         return model
 
     def build(self, local_rank: int) -> nn.Module:

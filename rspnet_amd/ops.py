@@ -456,6 +456,43 @@ class HipOps:
         self._log_hbm("bn_bwd(reduce+apply)", 4 * (2 * (n_in * (1 if residual is None else 2) + dout.numel()) + n_in * (2 if want_dres else 1)), e0)
         return dy, dres
 
+    def bn_eval_act_pool_bwd(self, pg: PoolGeom, y, residual, dout, mean_invstd, scale_shift, relu: bool, want_dres: bool,
+                             dgamma_out, dbeta_out, dy_out=None):
+        """Backward of bn_act_pool_fwd on RUNNING statistics (eval-mode BatchNorm), one pass: dy = scale * dz, dres = dz, and — when
+        asked for — dgamma = sum dz*xhat, dbeta = sum dz with xhat = (y - mean_invstd[0]) * mean_invstd[1].  scale_shift is what the
+        forward applied; mean_invstd holds running_mean - conv_bias and rsqrt(running_var + eps).  dgamma_out / dbeta_out may be
+        shorter than C (zero-padded channels: dy = 0 there).  dy_out as in bn_act_pool_bwd."""
+        in_ld = _rows_ld(y, "y")
+        d, dref, _, _ = _pool_plan(0, pg, in_ld, _rows_ld(dout, "dout"), None if residual is None else _rows_ld(residual, "residual"))
+        if dy_out is not None:
+            if _rows_ld(dy_out, "dy_out") != in_ld or dy_out.shape != y.shape:
+                raise _lib.RspError("dy_out: expected the shape and channel pitch of y")
+            dy = dy_out
+        else:
+            if not y.is_contiguous():
+                raise _lib.RspError("y is a channel slice: pass dy_out with the same pitch")
+            dy = torch.empty_like(y)
+        if want_dres and residual is None:
+            raise _lib.RspError("want_dres without a residual")
+        dres = torch.empty(y.shape, dtype=torch.float32, device=y.device) if want_dres else None
+        if want_dres and d.res_ld != pg.C:
+            raise _lib.RspError("residual: a residual whose gradient is wanted must be contiguous")
+        sums = dgamma_out is not None or dbeta_out is not None
+        c_valid = pg.C
+        for v in (dgamma_out, dbeta_out):
+            if v is not None:
+                c_valid = int(v.shape[0])
+        wsb = int(self.lib.rsp_bn_eval_bwd_workspace(dref)) if sums else 0
+        ws = self._workspace(y.device, wsb) if sums else None
+        e0 = self._ev()
+        _lib.check(self.lib.rsp_bn_eval_act_pool_bwd(dref, _ptr(y), _ptr(residual), _ptr(dout), _ptr(mean_invstd), _ptr(scale_shift),
+                                                     int(relu), _ptr(dy), _ptr(dres), _ptr(dgamma_out), _ptr(dbeta_out), c_valid,
+                                                     _ptr(ws), wsb, _stream()), "rsp_bn_eval_act_pool_bwd")
+        # one pass: y (+ residual) + dout read, dy (+ dres) written
+        n_in = y.numel()
+        self._log_hbm("bn_eval_bwd(one pass)", 4 * (n_in * (1 if residual is None else 2) + dout.numel() + n_in * (2 if want_dres else 1)), e0)
+        return dy, dres
+
     # ---- stand-alone pooling / gating --------------------------------------------------------------------------
     def maxpool_fwd(self, pg: PoolGeom, x, keep: bool):
         do, ho, wo = pg.out_dims
