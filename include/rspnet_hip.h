@@ -485,6 +485,33 @@ int rsp_xent_metrics(const float* logits, int32_t rows, int32_t classes, int32_t
                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The per-step bookkeeping of the pretext loop (pretext_metrics.hip; the reference's pretrain.py:167-195), one call: accuracy(topk=
+ * (1, 5)) of both contrast logit matrices, the top-1 of the ranking pair (framework/metrics/classification.py:6-20) and the eight
+ * AverageMeter.update calls (framework/meters/average.py:22-26).
+ * logits1, logits2: dense [B][K1] fp32 as rsp_logits_fwd writes them (rows start at r * K1 floats: 4-byte alignment is enough);
+ * the positive is column 0 (labels_A is all zeros).  lposM, lnegM: B fp32 each.  B >= 1, K1 >= 5.
+ *   rank(row) = #{c : v[c] > v[0]}: a column EQUAL to the positive does not count -- an exact tie goes to the lower index, the rule
+ *   of rsp_xent_metrics (torch.topk leaves it open) -- and a NaN column never counts.  A NaN positive is a miss.
+ *   acc [5]   (acc1_A, acc5_A, acc1_A_n, acc5_A_n, acc1_M) in percent, fp32(hits) * fp32(100.0 / B).  The first four: rank == 0 and
+ *             rank < 5 over logits1 / logits2; acc1_M counts rows with lposM >= lnegM (a NaN on either side is a miss).
+ *   losses    the [3] (loss, loss_A, loss_M) rsp_loss_fwd_bwd wrote; read only for the meters (may be NULL when meters is).
+ *   meters    device struct, may be NULL: val[i] = v_i, sum[i] += v_i * B (fp32), count[i] += B for the eight values in the struct's
+ *             order (losses[0], losses[1], acc[0..3], losses[2], acc[4]).
+ *   workspace 2 * B int32; after the call it holds the ranks, logits1's rows then logits2's (0x7fffffff for a NaN positive).
+ * A bad size, a null pointer or a workspace below rsp_pretext_metrics_workspace(B) is RSP_EINVAL before anything is launched.  Two
+ * kernel launches, no memset / memcpy, no atomics: capturable, and the same input gives the same bits.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct rsp_pretext_meters {  /* order: loss, loss_A, acc1_A, acc5_A, acc1_A_n, acc5_A_n, loss_M, acc1_M */
+  float val[8];
+  float sum[8];
+  int32_t count[8];
+} rsp_pretext_meters;
+size_t rsp_pretext_metrics_workspace(int32_t B);
+int rsp_pretext_metrics(const float* logits1, const float* logits2, const float* lposM, const float* lnegM, int32_t B, int32_t K1,
+                        const float* losses, float* acc, rsp_pretext_meters* meters, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Similarity maps of the pretext model and their picture panels (cam.hip): MoCoDiffLossTwoFc.cam_visualize
  * (moco/builder_diffspeed_diffloss.py:449-490) and what visualization.py:52-111 draws from its result.
  *

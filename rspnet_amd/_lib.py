@@ -58,6 +58,11 @@ class ClsMeters(C.Structure):
     _fields_ = [("val", C.c_float * 3), ("sum", C.c_float * 3), ("count", C.c_int32 * 3)]
 
 
+class PretextMeters(C.Structure):
+    """rsp_pretext_meters (96 bytes): loss, loss_A, acc1_A, acc5_A, acc1_A_n, acc5_A_n, loss_M, acc1_M"""
+    _fields_ = [("val", C.c_float * 8), ("sum", C.c_float * 8), ("count", C.c_int32 * 8)]
+
+
 _PD = C.POINTER(ConvDesc)
 _PP = C.POINTER(PoolDesc)
 _sz = C.c_size_t
@@ -152,6 +157,8 @@ SIGNATURES = {
     "rsp_topk_hits": (C.c_int, [_p, _i32, _i32, _p, _p, _i32, C.POINTER(C.c_int32), _i32, _p, _p]),
     "rsp_xent_metrics_workspace": (_sz, [_i32, _i32]),
     "rsp_xent_metrics": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "rsp_pretext_metrics_workspace": (_sz, [_i32]),
+    "rsp_pretext_metrics": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
     "rsp_cam_maps_workspace": (_sz, [_i32, _i32]),
     "rsp_cam_maps": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _sz, _p]),
     "rsp_cam_overlay": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),

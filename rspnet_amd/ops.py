@@ -765,6 +765,33 @@ class HipOps:
                                              wsb, _stream()), "rsp_xent_metrics")
         return avg, out[:1], out[1:], dlogits
 
+    # ---- pretext accuracies and meters (pretext_metrics.hip) -----------------------------------------------------
+    def pretext_metrics(self, logits1, logits2, lposM, lnegM, losses, meters_buf=None):
+        """The pretext loop's per-step accuracies and its eight meter updates in one call (rsp_pretext_metrics).  logits1 / logits2:
+        dense (B, K1) fp32 with the positive in column 0; lposM / lnegM: B fp32 each; losses: the (3,) fp32 (loss, loss_A, loss_M) of
+        loss_fwd_bwd; meters_buf: the 96-byte device struct (uint8 tensor) or None.  Returns acc (5,): acc1_A, acc5_A, acc1_A_n,
+        acc5_A_n, acc1_M in percent.  An exact tie with the positive goes to the positive; a NaN positive is a miss."""
+        for n, t in (("logits1", logits1), ("logits2", logits2), ("l_pos_M", lposM), ("l_neg_M", lnegM), ("losses", losses)):
+            _chk(t, n)
+        if logits1.dim() != 2 or logits2.shape != logits1.shape:
+            raise _lib.RspError(f"pretext_metrics: logits must be two (B, K1) matrices of one shape, got {tuple(logits1.shape)} and "
+                                f"{tuple(logits2.shape)}")
+        B, K1 = logits1.shape
+        if lposM.numel() != B or lnegM.numel() != B or losses.numel() != 3:
+            raise _lib.RspError(f"pretext_metrics: expected {B} ranking logits per side and 3 losses, got {lposM.numel()}, "
+                                f"{lnegM.numel()} and {losses.numel()}")
+        if meters_buf is not None:
+            _chk(meters_buf, "meters", torch.uint8)
+            if meters_buf.numel() < C.sizeof(_lib.PretextMeters):
+                raise _lib.RspError("pretext_metrics: meters must hold one rsp_pretext_meters")
+        dev = logits1.device
+        acc = torch.empty(5, dtype=torch.float32, device=dev)
+        wsb = int(self.lib.rsp_pretext_metrics_workspace(B))
+        ws = self._workspace(dev, wsb)
+        _lib.check(self.lib.rsp_pretext_metrics(_ptr(logits1), _ptr(logits2), _ptr(lposM), _ptr(lnegM), B, K1, _ptr(losses), _ptr(acc),
+                                                _ptr(meters_buf), _ptr(ws), wsb, _stream()), "rsp_pretext_metrics")
+        return acc
+
     # ---- similarity maps and their picture panels (cam.hip) --------------------------------------------------------
     def cam_maps(self, feat_q, feat_k, k_row, w_qA, w_qM, w_kA, w_kM):
         """The four similarity maps of MoCoDiffLossTwoFc.cam_visualize from the two NDHWC feature maps (B, T', H', W', C) — dense, or

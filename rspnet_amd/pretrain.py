@@ -3,7 +3,8 @@ checkpoint layout, LR policy) around the MI355X-native step.
 
 Mirrors /root/reference/pretrain.py:31-336 for what touches the hot path: Engine construction (:33-110: model factory,
 Loss(margin=2.0, A, M), LR scaling, SGD, CosineAnnealingLR per epoch with eta_min = lr/1000), checkpoint load with the arch
-check (:112-132), the train loop (:147-197: forward, loss, zero_grad/backward/step, top-k accuracies), epoch loop and
+check (:112-132), the train loop (:147-218: forward, loss, zero_grad/backward/step or `--validate`, the top-k accuracies and the
+eight meters as ONE HIP call per step, rsp_pretext_metrics, the log wording, per-epoch scalars to scalars.jsonl), epoch loop and
 checkpoint dict (:220-260), one process per GPU started with mp.spawn and a tcp://127.0.0.1 rendezvous (:263-336).
 The data pipeline (decord decode + GPU augmentation) is out of scope: the loader here is any iterable
 of (clip_q, clip_k) device tensors; `SyntheticClips` stands in for it.  The config is the resolved JSON the reference
@@ -12,6 +13,7 @@ saves as run_*/config.json (rspnet_amd/config/pretrain/*.json ship the four ship
 from __future__ import annotations
 
 import argparse
+import ctypes
 import json
 import logging
 import math
@@ -24,9 +26,11 @@ from datetime import datetime
 from pathlib import Path
 from shlex import quote
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import _lib, ops
 from .framework.utils.checkpoint import CheckpointManager
 from .framework.utils.environment import scale_learning_rate
 from .moco import Loss, ModelFactory
@@ -42,6 +46,79 @@ def accuracy(output: torch.Tensor, target: torch.Tensor, topk=(1,)):
     _, pred = output.topk(maxk, 1, True, True)
     correct = pred.t().eq(target.view(1, -1).expand_as(pred.t()))
     return [correct[:k].reshape(-1).float().sum(0) * (100.0 / target.size(0)) for k in topk]
+
+
+def pretext_accuracy(output, ranking_logits) -> torch.Tensor:
+    """(acc1_A, acc5_A, acc1_A_n, acc5_A_n, acc1_M) in percent as one (5,) tensor: what pretrain.py:169-172 takes from
+    accuracy(output[0], 0, (1, 5)), accuracy(output[1], 0, (1, 5)) and accuracy(cat(ranking_logits), 0, (1,)), restated on the rank of
+    the positive (column 0), rank = #{c : v[c] > v[0]}, with the tie rule of rsp_pretext_metrics: a column equal to the positive does
+    not count, a NaN positive is a miss, l_pos_M == l_neg_M is a hit.  Torch ops, any device; no sync."""
+    B = output[0].shape[0]
+    hits = []
+    for logits in output:
+        pos = logits[:, :1]
+        rank = (logits > pos).sum(dim=1)
+        ok = (pos == pos).view(-1)
+        hits += [((rank == 0) & ok).sum(), ((rank < 5) & ok).sum()]
+    hits.append((ranking_logits[0].reshape(-1) >= ranking_logits[1].reshape(-1)).sum())
+    return torch.stack(hits).to(torch.float32) * (100.0 / B)                      # classification.py:18-19
+
+
+class PretextMeters:
+    """The eight running meters of a pretext epoch (pretrain.py:97-106; framework/meters/average.py) as ONE device struct,
+    rsp_pretext_meters: val[8] / sum[8] fp32, count[8] int32.  rsp_pretext_metrics updates it on the device; ``read`` is the only
+    host synchronisation."""
+
+    NAMES = ("Loss", "Loss_A", "Acc@1_A", "Acc@5_A", "Acc@1_A_n", "Acc@5_A_n", "Loss_M", "Acc@1_M")
+    KEYS = ("loss", "loss_A", "acc1_A", "acc5_A", "acc1_A_n", "acc5_A_n", "loss_M", "acc1_M")
+    FMTS = (":f", ":f", ":6.2f", ":6.2f", ":6.2f", ":6.2f", ":f", ":6.2f")
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.buf = torch.zeros(ctypes.sizeof(_lib.PretextMeters), dtype=torch.uint8, device=self.device)
+        self.val = self.buf[0:32].view(torch.float32)
+        self.sum = self.buf[32:64].view(torch.float32)
+        self.count = self.buf[64:96].view(torch.int32)
+
+    def reset(self):
+        self.buf.zero_()
+
+    @torch.no_grad()
+    def update(self, values, n: int):
+        """AverageMeter.update(v_i, n) for the eight values in KEYS order from torch ops -- the path of a backend without the HIP
+        entry point, and of host tensors."""
+        v = torch.stack([x.detach().to(torch.float32).reshape(()) for x in values]).to(self.device)
+        self.val.copy_(v)
+        self.sum += v * n
+        self.count += n
+
+    def read(self):
+        """{key: {val, avg, sum, count}}; avg = sum / count in fp32 (NaN while count is 0).  Synchronises."""
+        host = self.buf.cpu().numpy()
+        val, total, count = host[0:32].view(np.float32), host[32:64].view(np.float32), host[64:96].view(np.int32)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            avg = total / count.astype(np.float32)
+        return {k: {"val": float(val[i]), "avg": float(avg[i]), "sum": float(total[i]), "count": int(count[i])}
+                for i, k in enumerate(self.KEYS)}
+
+    def pieces(self, stats=None):
+        """['Loss {val:f} ({avg:f})', 'Loss_A ...', 'Acc@1_A {val:6.2f} ({avg:6.2f})', ...] as AverageMeter.__str__ formats them."""
+        stats = stats or self.read()
+        return [("{name} {val" + fmt + "} ({avg" + fmt + "})").format(name=name, val=stats[k]["val"], avg=stats[k]["avg"])
+                for name, k, fmt in zip(self.NAMES, self.KEYS, self.FMTS)]
+
+    def __str__(self):
+        return "\t".join(self.pieces())
+
+
+def _losses3(loss, loss_A, loss_M) -> torch.Tensor:
+    """The step's (loss, loss_A, loss_M) as one (3,) tensor: the buffer rsp_loss_fwd_bwd wrote when the three are its elements (no
+    launch), a stack otherwise."""
+    loss = loss.detach()
+    if (loss.dim() == 0 and loss.dtype == torch.float32 and loss_A.data_ptr() == loss.data_ptr() + 4
+            and loss_M.data_ptr() == loss.data_ptr() + 8):
+        return torch.as_strided(loss, (3,), (1,), loss.storage_offset())
+    return torch.stack([loss, loss_A.detach(), loss_M.detach()]).to(torch.float32)
 
 
 class SyntheticClips:
@@ -128,6 +205,9 @@ class Engine:
         self.log_interval = int(cfg["log_interval"])
         self.current_epoch = 0
         self.best_loss = math.inf
+        self.meters, self.stats = None, None
+        run_dir = getattr(args, "run_dir", None)
+        self.scalars_path = None if run_dir is None or local_rank != 0 else Path(run_dir) / "scalars.jsonl"
         T, size = int(cfg["temporal_transforms"]["size"]), int(cfg["spatial_transforms"]["size"])
         if train_loader is None and getattr(args, "loader", "tensor") == "uint8":
             train_loader = SyntheticVideoClips(self.batch_size, T, size, args.steps_per_epoch, self.device,
@@ -154,11 +234,29 @@ class Engine:
         self.model.module.load_state_dict(self._load_ckpt_file(path)["model"])
 
     # ---- training (pretrain.py:147-260) ------------------------------------------------------------------------------
-    def train_epoch(self):
-        sums = torch.zeros(4, device=self.device)
+    def _update_meters(self, loss, loss_A, loss_M, output, ranking_logits):
+        """The step's accuracies and the eight meter updates (pretrain.py:167-195): ONE rsp_pretext_metrics call, issued behind the
+        step; torch ops on a backend without the entry point."""
+        be = ops.backend()
+        if hasattr(be, "pretext_metrics"):
+            be.pretext_metrics(output[0].contiguous(), output[1].contiguous(), ranking_logits[0].contiguous(),
+                               ranking_logits[1].contiguous(), _losses3(loss, loss_A, loss_M), self.meters.buf)
+        else:
+            acc = pretext_accuracy(output, ranking_logits)
+            self.meters.update([loss, loss_A, acc[0], acc[1], acc[2], acc[3], loss_M, acc[4]], output[0].shape[0])
+
+    def train_epoch(self, validate: bool = False):
+        """One pass over the loader (pretrain.py:147-218).  validate (--validate, :162): forward, loss and meters only -- no
+        zero_grad / backward / step and no graph capture; the model's own state (key encoder, queue, BatchNorm statistics) moves as
+        a forward moves it, the parameters of encoder_q do not change."""
+        if self.meters is None:
+            self.meters = PretextMeters(self.device)
+        self.meters.reset()
         n = 0
+        num_iters = len(self.train_loader)
         t0 = time.perf_counter()
-        if self._stepper is None and self.device.type == "cuda" and not getattr(self.args, "no_graph", False):
+        if (not validate and self._stepper is None and self.device.type == "cuda"
+                and not getattr(self.args, "no_graph", False)):
             # the five statements below run through the stepper — replayed as linear HIP graphs on three streams, with the
             # data-parallel collectives between them at more than one rank, where the host cannot issue the step fast enough; the
             # eager loop with its side streams otherwise (rspnet_amd/graph_step.py)
@@ -171,37 +269,56 @@ class Engine:
                 import gc
                 gc.collect()
                 gc.freeze()
-            if self._stepper is not None:
+            if self._stepper is not None and not validate:
                 loss, loss_A, loss_M, output, ranking_logits = self._stepper(clip_q, clip_k)
-                target = torch.zeros(output[0].shape[0], dtype=torch.long, device=output[0].device)   # labels_A (:540)
             else:
                 output, target, ranking_logits, ranking_target = self.model(clip_q, clip_k)
                 loss, loss_A, loss_M = self.criterion(output, target, ranking_logits, ranking_target)
-                self.optimizer.zero_grad()
-                loss.backward()
-                self.optimizer.step()
-            acc1_A, acc5_A = accuracy(output[0], target, topk=(1, 5))
-            acc1_M, = accuracy(torch.cat(ranking_logits, dim=1), target, topk=(1,))
-            sums += torch.stack([loss.detach(), loss_A, loss_M, acc1_A])
+                if not validate:
+                    self.optimizer.zero_grad()
+                    loss.backward()
+                    self.optimizer.step()
+            if self.local_rank == 0 and it > 0 and it % self.log_interval == 0:
+                # numbers from the last iteration, just before this one's update (pretrain.py:177-185); the only host sync
+                p = self.meters.pieces()
+                logger.info(f"Train [{self.current_epoch}/{self.num_epochs}][{it - 1}/{num_iters}]"
+                            f"\t{p[1]}\t{p[2]}\t{p[3]}\n{p[6]}\t{p[7]}\n{p[4]}\t{p[5]}")
+            # the stepper's tensors are the graphs' output buffers: consumed here, before the next step overwrites them
+            self._update_meters(loss, loss_A, loss_M, output, ranking_logits)
             n += 1
-            if self.local_rank == 0 and (it + 1) % self.log_interval == 0:    # the only host sync (pretrain.py:177-185)
-                m = (sums / n).tolist()
-                logger.info("epoch %d it %d loss %.4f loss_A %.4f loss_M %.4f acc1_A %.2f acc1_M %.2f", self.current_epoch,
-                            it + 1, m[0], m[1], m[2], m[3], float(acc1_M))
         torch.cuda.synchronize(self.device)
         dt = time.perf_counter() - t0
-        mean = (sums / max(n, 1)).tolist()
-        return {"loss": mean[0], "loss_A": mean[1], "loss_M": mean[2], "acc1_A": mean[3],
-                "clips_per_s": n * self.batch_size * self.args.world_size / dt}
+        self.stats = self.meters.read()
+        out = {k: self.stats[k]["avg"] for k in ("loss", "loss_A", "loss_M", "acc1_A", "acc5_A", "acc1_A_n", "acc5_A_n", "acc1_M")}
+        out["clips_per_s"] = n * self.batch_size * self.args.world_size / dt
+        return out
+
+    def _write_scalars(self, lr: float):
+        """One line per epoch in RUN_DIR/scalars.jsonl (rank 0): what pretrain.py:199-218,240 hands to the summary writer."""
+        if self.scalars_path is None:
+            return
+        rec = {"epoch": self.current_epoch, "train/lr": lr}
+        rec.update({f"train/{k}": self.stats[k]["avg"] for k in ("loss", "loss_A", "acc1_A", "acc5_A", "loss_M", "acc1_M")})
+        self.scalars_path.parent.mkdir(parents=True, exist_ok=True)
+        with open(self.scalars_path, "a") as f:
+            f.write(json.dumps(rec) + "\n")
 
     def run(self):
         num_epochs = 1 if self.args.debug else self.num_epochs
         self._first_epoch = self.current_epoch
         self.model.train()
         stats = None
+        if getattr(self.args, "validate", False):
+            # --validate (pretrain.py:162): the loop body without the optimisation; one epoch, nothing is saved
+            stats = self.train_epoch(validate=True)
+            if self.local_rank == 0:
+                logger.info("validate epoch %d done: %s", self.current_epoch, json.dumps(stats))
+            return stats
         while self.current_epoch < num_epochs:
+            lr = float(self.optimizer.param_groups[0]["lr"])
             stats = self.train_epoch()
             self.scheduler.step()
+            self._write_scalars(lr)
             self.current_epoch += 1
             self.model.sync_buffers()
             if self.local_rank == 0:
@@ -336,6 +453,8 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-scale-lr", action="store_true")
     ap.add_argument("--steps-per-epoch", type=int, default=100, help="synthetic loader length")
+    ap.add_argument("--validate", action="store_true",
+                    help="one epoch of forward, loss and meters without optimisation (pretrain.py:162)")
     ap.add_argument("--no-graph", action="store_true", help="never replay the step as captured HIP graphs (default: only when the host is the limiter)")
     ap.add_argument("--loader", choices=("tensor", "uint8"), default="tensor",
                     help="tensor: fixed N(0,1) device clips; uint8: synthetic uint8 videos -> CPU random crop -> fused GPU augmentation")
