@@ -35,6 +35,9 @@ const char* rsp_last_error(void);
 /* Demangled template instance of the FIRST matrix kernel the calling thread's most recent rsp_conv3d_{fwd,dgrad,dgrad_packed,
  * wgrad} call launched (written by the launcher itself; "" if the call launched none).  Cross-checks rsp_conv3d_kernel_name. */
 const char* rsp_last_conv_kernel(void);
+/* ABI version.  130 folded every operation's suffixed variants (_v, _x, _t, _g, _gate_) into ONE entry point under the plain name
+ * with the full argument list, and dropped the stand-alone per-channel statistics pass that no convolution on the path needed: a
+ * binding written against 120 must be re-checked against the declarations below. */
 int rsp_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------
@@ -106,23 +109,20 @@ int32_t rsp_conv3d_pack_jobs(const rsp_conv3d_desc* d, int32_t which, int32_t Co
 int rsp_pack_run(const rsp_pack_job* jobs_device, int32_t n_jobs, int32_t max_blocks, void* stream);
 void rsp_conv3d_pack_forget(const void* w_packed);
 
-/* wgrad: dw (reference layout, overwritten) = sum over positions of dy ⊗ im2col(x); dbias (nullable) = sum dy. */
+/* wgrad: dw (reference layout, overwritten) = sum over positions of dy ⊗ im2col(x); dbias (nullable) = sum dy.
+ *   cout_valid, cin_valid: the parameter's own channel counts.  A convolution may run with its channels zero padded in the
+ *     descriptor (d->Cout / d->Cin) but not in the parameter: dw_ref is (cout_valid, cin_valid, kT, kH, kW) and the gradients of the
+ *     padding channels are dropped.  Unpadded: pass d->Cout and d->Cin.  dbias only with unpadded channels.
+ *   rowgeom_table (nullable): the kernels stream a per-row geometry table (input byte offset + padding-validity bits of each output
+ *     position: a function of the geometry alone).  With NULL it is computed in a pre-pass of the call, in the workspace; a caller
+ *     that keeps one table per geometry (rsp_conv3d_rowgeom_bytes, rsp_conv3d_rowgeom: one launch, once) passes it here and saves
+ *     that launch — 59 per S3D-G step.
+ * workspace and table 16-byte aligned. */
 size_t rsp_conv3d_wgrad_workspace(const rsp_conv3d_desc* d);
-int rsp_conv3d_wgrad(const rsp_conv3d_desc* d, const float* x, const float* dy, float* dw_ref, float* dbias,
-                     void* workspace, size_t workspace_bytes, void* stream);
-/* The same for a convolution whose channels are zero padded in the descriptor (d->Cout / d->Cin) but not in the parameter:
- * dw_ref is (cout_valid, cin_valid, kT, kH, kW), the gradients of the padding channels are dropped.  dbias must be NULL. */
-int rsp_conv3d_wgrad_v(const rsp_conv3d_desc* d, const float* x, const float* dy, float* dw_ref, int32_t cout_valid,
-                       int32_t cin_valid, void* workspace, size_t workspace_bytes, void* stream);
-
-/* The weight-gradient kernels stream a per-row geometry table (input byte offset + padding-validity bits of each output position:
- * a function of the geometry alone).  rsp_conv3d_wgrad / _v compute it in a pre-pass of every call; a caller that keeps one table
- * per geometry (rsp_conv3d_rowgeom_bytes, rsp_conv3d_rowgeom: one launch, once) passes it to rsp_conv3d_wgrad_t and saves that
- * launch — 59 per S3D-G step.  rowgeom_table may be NULL (then as rsp_conv3d_wgrad_v; dbias only with unpadded channels). */
 size_t rsp_conv3d_rowgeom_bytes(const rsp_conv3d_desc* d);
 int rsp_conv3d_rowgeom(const rsp_conv3d_desc* d, void* table, void* stream);
-int rsp_conv3d_wgrad_t(const rsp_conv3d_desc* d, const float* x, const float* dy, float* dw_ref, float* dbias, int32_t cout_valid,
-                       int32_t cin_valid, const void* rowgeom_table, void* workspace, size_t workspace_bytes, void* stream);
+int rsp_conv3d_wgrad(const rsp_conv3d_desc* d, const float* x, const float* dy, float* dw_ref, float* dbias, int32_t cout_valid,
+                     int32_t cin_valid, const void* rowgeom_table, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Name of the kernel template instance the library launches for this descriptor (which: 0 forward, 1 dgrad, 2 wgrad;
  * 16-byte aligned tensors assumed) -- lets bench.py label its roofline block with the kernel that actually dominates a
@@ -166,27 +166,18 @@ int rsp_fastdiv_check(int d, int n);
 /* Reduce stat partials -> mean (incl. conv bias), invstd; update running stats
  * (running_var with the unbiased n/(n-1) estimate), as F.batch_norm(training=True) does.
  * count = number of positions per channel.  scale_shift out: [2][C] = (gamma*invstd, beta - mean*gamma*invstd).
- * stat_ld (>= C) = channels per partial row: the C channels may be a slice of a wider convolution's partials (several
- * BasicConv3d that share their input run as ONE GEMM over the concatenated filters, models/s3dg.py:80-88). */
-size_t rsp_bn_finalize_workspace(int32_t tiles, int32_t C);
-int rsp_bn_finalize(const float* stat_partials, int32_t tiles, int32_t C, int32_t stat_ld, int64_t count, const float* conv_bias,
-                    const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                    float* running_var, float* mean_invstd /*[2][C]*/, float* scale_shift /*[2][C]*/, void* workspace,
-                    size_t workspace_bytes, void* stream);
-/* The same over a convolution that ran with its output channels zero-padded from c_valid to C (models/r2plus1d_vcop.py:35-38: mid
- * channel counts such as 83 / 230 / 921 run as 84 / 232 / 924 so that rows are 16 bytes aligned): conv_bias / gamma / beta /
- * running_mean / running_var hold c_valid entries; channels [c_valid, C) get scale = shift = 0 and move no running statistic. */
-int rsp_bn_finalize_v(const float* stat_partials, int32_t tiles, int32_t C, int32_t c_valid, int32_t stat_ld, int64_t count,
-                      const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                      float* running_var, float* mean_invstd /*[2][C]*/, float* scale_shift /*[2][C]*/, void* workspace,
-                      size_t workspace_bytes, void* stream);
-
-/* Deferred running statistics.  With batch_stats_out != NULL rsp_bn_finalize_x does NOT move running_mean / running_var (both
- * ignored) but writes this pass's batch moments — [2][c_valid]: mean (conv bias included), unbiased variance; rsp_bn_running_update
- * later applies  r = (1 - momentum) r + momentum * moment  for a whole list of layers in one launch (jobs in device memory), the
- * update nn.BatchNorm3d does inside forward.  The two key-encoder passes of a step (builder_diffspeed_diffloss.py:445,512) go through
- * the SAME BatchNorm buffers; deferring the second pass's update lets the passes run side by side in a captured graph and still
- * leaves the buffers as two consecutive forwards would. */
+ *   stat_ld (>= C) = channels per partial row: the C channels may be a slice of a wider convolution's partials (several
+ *     BasicConv3d that share their input run as ONE GEMM over the concatenated filters, models/s3dg.py:80-88).
+ *   c_valid: the parameter's own length.  A convolution may run with its output channels zero-padded from c_valid to C
+ *     (models/r2plus1d_vcop.py:35-38: mid channel counts such as 83 / 230 / 921 run as 84 / 232 / 924 so that rows are 16 bytes
+ *     aligned): conv_bias / gamma / beta / running_mean / running_var hold c_valid entries; channels [c_valid, C) get
+ *     scale = shift = 0 and move no running statistic.  Unpadded: pass C.
+ *   batch_stats_out (nullable): deferred running statistics.  When given, running_mean / running_var are NOT moved (both ignored)
+ *     and this pass's batch moments are written instead — [2][c_valid]: mean (conv bias included), unbiased variance;
+ *     rsp_bn_running_update later applies  r = (1 - momentum) r + momentum * moment  for a whole list of layers in one launch (jobs
+ *     in device memory), the update nn.BatchNorm3d does inside forward.  The two key-encoder passes of a step
+ *     (builder_diffspeed_diffloss.py:445,512) go through the SAME BatchNorm buffers; deferring the second pass's update lets the
+ *     passes run side by side in a captured graph and still leaves the buffers as two consecutive forwards would. */
 typedef struct rsp_bn_ema_job {
   float* running_mean;
   float* running_var;
@@ -194,16 +185,12 @@ typedef struct rsp_bn_ema_job {
   int32_t C;
   float momentum;
 } rsp_bn_ema_job;
-int rsp_bn_finalize_x(const float* stat_partials, int32_t tiles, int32_t C, int32_t c_valid, int32_t stat_ld, int64_t count,
-                      const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                      float* running_var, float* batch_stats_out, float* mean_invstd, float* scale_shift, void* workspace,
-                      size_t workspace_bytes, void* stream);
+size_t rsp_bn_finalize_workspace(int32_t tiles, int32_t C);
+int rsp_bn_finalize(const float* stat_partials, int32_t tiles, int32_t C, int32_t c_valid, int32_t stat_ld, int64_t count,
+                    const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
+                    float* running_var, float* batch_stats_out, float* mean_invstd /*[2][C]*/, float* scale_shift /*[2][C]*/,
+                    void* workspace, size_t workspace_bytes, void* stream);
 int rsp_bn_running_update(const rsp_bn_ema_job* jobs_device, int32_t n_jobs, int32_t max_c, void* stream);
-
-/* Standalone per-channel statistics of y (for convs whose epilogue did not produce partials): writes
- * [tiles][C][2] partials with tiles = rsp_bn_stat_tiles(rows). */
-int32_t rsp_bn_stat_tiles(int64_t rows);
-int rsp_bn_stats(const float* y, int64_t rows, int32_t C, int32_t ld, float* stat_partials, void* stream);
 
 typedef struct rsp_pool3d_desc {
   int32_t N, Di, Hi, Wi, C;
@@ -212,53 +199,42 @@ typedef struct rsp_pool3d_desc {
   int32_t in_ld, out_ld, res_ld;
 } rsp_pool3d_desc;
 
-/* out = maxpool(act(scale*y + shift (+ residual))) ; act = ReLU if relu!=0.  residual (nullable) has y's shape. */
+/* out = maxpool(act(scale*y + shift (+ residual)) (* gate)) ; act = ReLU if relu!=0.  residual (nullable) has y's shape.
+ *   gate (nullable): per-sample channel gates [N][C], multiplied in after the activation and before the max (see rsp_bn_gate_sums). */
 int rsp_bn_act_pool_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, const float* residual,
-                        int relu, float* out, void* stream);
-/* ... with per-sample channel gates ([N][C], nullable) multiplied in after the activation and before the max (see rsp_bn_gate_sums) */
-int rsp_bn_act_pool_gate_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, const float* residual,
-                             int relu, const float* gate, float* out, void* stream);
+                        int relu, const float* gate, float* out, void* stream);
 
 /* The ResNet stems' bn1 -> relu -> MaxPool3d(3, 2, 1) (models/resnet.py:139,203-207) — BatchNorm apply and an OVERLAPPING 3x3x3 or
- * 1x3x3 max-pool (any stride / padding) in one pass over the convolution output: out = maxpool(act(scale*y + shift)); argmax
+ * 1x3x3 max-pool (any stride / padding) in one pass over the convolution output: out = maxpool(act(scale*y + shift) (* gate)); argmax
  * (nullable) as rsp_maxpool3d_fwd writes it (first maximum in scan order, linear input position per sample), so that
  * rsp_maxpool3d_bwd and then rsp_bn_act_pool_bwd (unit window) form its backward.  Bit-identical to rsp_bn_act_pool_fwd with a unit
  * window followed by rsp_maxpool3d_fwd; the activated tensor is neither written nor read.  rsp_bn_act_pool_fwd takes this path
  * itself for such windows (no residual).  Needs C, in_ld, out_ld multiples of 4 and 16-byte aligned pointers
- * (rsp_bn_act_maxpool_applicable). */
+ * (rsp_bn_act_maxpool_applicable).
+ *   gate (nullable): S3D-G's per-sample channel gates [N][C], multiplied in between the activation and the pool
+ *     (models/s3dg.py:105-108: the two front-end sep_conv units are followed by (1,3,3) / (1,2,2) max-pools): rsp_bn_gate_sums ->
+ *     this, instead of rsp_bn_act_pool_fwd (unit window) -> rsp_maxpool3d_fwd; same bits. */
 int rsp_bn_act_maxpool_applicable(const rsp_pool3d_desc* d);
-int rsp_bn_act_maxpool_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, int relu, float* out, int32_t* argmax,
-                           void* stream);
-/* ... with S3D-G's per-sample channel gates ([N][C], nullable) multiplied in between the activation and the pool (models/s3dg.py:105-108:
- * the two front-end sep_conv units are followed by (1,3,3) / (1,2,2) max-pools): rsp_bn_gate_sums -> this, instead of
- * rsp_bn_act_pool_gate_fwd (unit window) -> rsp_maxpool3d_fwd; same bits, and rsp_bn_act_pool_gate_fwd takes this path itself. */
-int rsp_bn_act_maxpool_gate_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, int relu, const float* gate, float* out,
-                                int32_t* argmax, void* stream);
+int rsp_bn_act_maxpool_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, int relu, const float* gate, float* out,
+                           int32_t* argmax, void* stream);
 
 /* Backward of the fused block, two launches:
  *  reduce: per-channel partial sums of dz and dz*xhat (dz = grad at the BN output after pool routing + ReLU mask)
  *  apply : dy = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)); also d(residual) = dz (if dres != NULL),
  *          dgamma = sum(dz*xhat), dbeta = sum(dz).
- * The pooled activation is recomputed from y (saved conv output), never stored. */
+ * The pooled activation is recomputed from y (saved conv output), never stored.
+ *   c_valid: the parameter's own length, as in rsp_bn_finalize: gamma / dgamma / dbeta hold c_valid entries; the padding channels
+ *     [c_valid, C) have gamma = 0.  Unpadded: pass d->C.
+ *   gate, dmean (both or neither): the block sits behind an S3D-G self-gating unit whose forward kept no activation
+ *     (rsp_bn_gate_sums, act == NULL): dout is the gradient of the GATED output; gate [N][C] from the forward, dmean [N][C] from
+ *     rsp_gate_bwd_params.  Unit windows, no residual. */
 size_t rsp_bn_bwd_workspace(const rsp_pool3d_desc* d);
 int rsp_bn_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
                         const float* gamma, const float* mean_invstd, const float* scale_shift, int relu, float* dy,
-                        float* dres, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
-                        void* stream);
-/* channel-padded variant (see rsp_bn_finalize_v): gamma / dgamma / dbeta hold c_valid entries; padding channels have gamma = 0 */
-int rsp_bn_act_pool_bwd_v(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
-                          const float* gamma, const float* mean_invstd, const float* scale_shift, int relu, float* dy,
-                          float* dres, float* dgamma, float* dbeta, int32_t c_valid, void* workspace, size_t workspace_bytes,
-                          void* stream);
+                        float* dres, float* dgamma, float* dbeta, int32_t c_valid, const float* gate, const float* dmean,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
-/* ... behind an S3D-G self-gating unit whose forward kept no activation (rsp_bn_gate_sums, act == NULL): dout is the gradient of
- * the GATED output; gate [N][C] from the forward, dmean [N][C] from rsp_gate_bwd_params.  Unit windows, no residual. */
-int rsp_bn_act_pool_bwd_g(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
-                          const float* gamma, const float* mean_invstd, const float* scale_shift, int relu, float* dy,
-                          float* dres, float* dgamma, float* dbeta, int32_t c_valid, const float* gate, const float* dmean,
-                          void* workspace, size_t workspace_bytes, void* stream);
-
-/* Eval-mode counterpart of rsp_bn_act_pool_bwd_v — BatchNorm on its running statistics — in ONE pass over y and dout:
+/* Eval-mode counterpart of rsp_bn_act_pool_bwd — BatchNorm on its running statistics — in ONE pass over y and dout:
  *   dz = gradient at the BatchNorm output after pool routing + ReLU mask, recomputed from y with the forward's tie rule
  *   dy = scale*dz (0 on the padding channels [c_valid, C)); d(residual) = dz (if dres != NULL)
  *   dgamma = sum(dz*xhat), dbeta = sum(dz), xhat = (y - mean')*invstd          (both nullable, c_valid entries)
@@ -266,7 +242,7 @@ int rsp_bn_act_pool_bwd_g(const rsp_pool3d_desc* d, const float* y, const float*
  * rsqrt(running_var + eps) and is read only when a parameter gradient is asked for.  With dgamma == dbeta == NULL no sums are
  * formed and neither mean_invstd nor the workspace is touched (frozen affine parameters).  Otherwise every workgroup writes its
  * partial sums to the workspace and one small launch adds them in a fixed order: no atomics, bit-identical run to run.  Same
- * geometry conventions as rsp_bn_act_pool_bwd_v (disjoint windows of any size, separate pitches for y / dout / residual). */
+ * geometry conventions as rsp_bn_act_pool_bwd (disjoint windows of any size, separate pitches for y / dout / residual). */
 size_t rsp_bn_eval_bwd_workspace(const rsp_pool3d_desc* d);
 int rsp_bn_eval_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
                              const float* mean_invstd, const float* scale_shift, int relu, float* dy, float* dres,
@@ -288,7 +264,7 @@ int rsp_gate_fwd(const float* x, int32_t N, int32_t P, int32_t C, int32_t in_ld,
  * (sep_conv = ... BasicConv3d -> excitation, models/s3dg.py:52-72): rsp_bn_gate_sums computes a = relu(y*scale + shift), its
  * per-(sample, channel) mean and the gate in one pass over y — storing a ([N][P][C], pitch act_ld) only when `act` is given (a
  * backward will read it) — and the gated output is then either rsp_gate_apply(a) or, without the stored activation,
- * rsp_bn_act_pool_gate_fwd straight from y (optionally through the max-pool that follows the front-end units, s3dg.py:105-109).
+ * rsp_bn_act_pool_fwd (with the gate) straight from y (optionally through the max-pool that follows the front-end units, s3dg.py:105-109).
  * Bit-identical to rsp_bn_act_pool_fwd + rsp_gate_fwd (+ rsp_maxpool3d_fwd).  Workspace: rsp_gate_fwd_workspace(N, P, C). */
 int rsp_bn_gate_sums(const float* y, int32_t N, int32_t P, int32_t C, int32_t y_ld, const float* scale_shift, int relu,
                      float* act, int32_t act_ld, const float* w, const float* b, float* mean, float* gate, void* workspace,
@@ -296,7 +272,7 @@ int rsp_bn_gate_sums(const float* y, int32_t N, int32_t P, int32_t C, int32_t y_
 int rsp_gate_apply(const float* x, int32_t N, int32_t P, int32_t C, int32_t in_ld, const float* gate, float* out, int32_t out_ld,
                    void* stream);
 /* Parameter half of the gating backward with the activation recomputed from y: dw (C,C), db (C) and dmean [N][C] (the data half
- * runs inside rsp_bn_act_pool_bwd_g).  Workspace: rsp_gate_bwd_workspace(N, P, C). */
+ * runs inside rsp_bn_act_pool_bwd).  Workspace: rsp_gate_bwd_workspace(N, P, C). */
 int rsp_gate_bwd_params(const float* y, const float* scale_shift, int relu, const float* dout, int32_t N, int32_t P, int32_t C,
                         int32_t y_ld, int32_t dout_ld, const float* w, const float* mean, const float* gate, float* dw, float* db,
                         float* dmean, void* workspace, size_t workspace_bytes, void* stream);

@@ -182,32 +182,6 @@ __global__ __launch_bounds__(1024) void bn_finalize_one_kernel(const float* __re
   if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
 }
 
-// standalone stats over 128-row tiles (same partial layout as the conv epilogue)
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ y, long long rows, int C, int ld,
-                                                       float* __restrict__ part) {
-  __shared__ float red[4][64][2];
-  const int tile = blockIdx.x;
-  const int c = blockIdx.y * 64 + (threadIdx.x & 63);
-  const int rl = threadIdx.x >> 6;
-  float s = 0.f, ss = 0.f;
-  if (c < C)
-    for (int r = rl; r < 128; r += 4) {
-      const long long row = (long long)tile * 128 + r;
-      if (row >= rows) break;
-      const float v = y[row * ld + c];
-      s += v;
-      ss = fmaf(v, v, ss);
-    }
-  red[rl][threadIdx.x & 63][0] = s;
-  red[rl][threadIdx.x & 63][1] = ss;
-  __syncthreads();
-  if (rl == 0 && c < C) {
-    const int l = threadIdx.x;
-    part[((long long)tile * C + c) * 2 + 0] = red[0][l][0] + red[1][l][0] + red[2][l][0] + red[3][l][0];
-    part[((long long)tile * C + c) * 2 + 1] = red[0][l][1] + red[1][l][1] + red[2][l][1] + red[3][l][1];
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // forward: out = maxpool(act(scale*y + shift + res))
 // ------------------------------------------------------------------------------------------------------------------
@@ -246,6 +220,12 @@ static Layout make_layout(const rsp_pool3d_desc* d, int cg, int per_thread) {
   b = b > 16384 ? 16384 : (b < 1 ? 1 : b);
   L.grid = dim3((unsigned)b, (unsigned)rsp_cdiv(cg, 256));
   return L;
+}
+
+// copies the thread layout into the parameter struct of a kernel that walks it (PoolParams, BwdParams)
+template <typename P>
+static void set_layout(P& p, const Layout& L) {
+  p.cgc = L.cgc; p.ppi = L.ppi; p.npos = L.npos; p.dcgc = L.dcgc; p.dWo = L.dWo; p.dHo = L.dHo; p.dDo = L.dDo;
 }
 
 template <int VEC>
@@ -1192,15 +1172,6 @@ int reduce_blocks(const rsp_pool3d_desc* d, int cg) {
 
 extern "C" {
 
-int32_t rsp_bn_stat_tiles(int64_t rows) { return rsp_cdiv(rows, 128); }
-
-int rsp_bn_stats(const float* y, int64_t rows, int32_t C, int32_t ld, float* stat_partials, void* stream) {
-  RSP_REQUIRE(y && stat_partials && rows > 0 && C > 0 && ld >= C, "rsp_bn_stats: bad argument");
-  dim3 grid(rsp_cdiv(rows, 128), rsp_cdiv(C, 64));
-  hipLaunchKernelGGL(bn_stats_kernel, grid, dim3(256), 0, (hipStream_t)stream, y, (long long)rows, C, ld, stat_partials);
-  return rsp_check_launch("bn_stats_kernel");
-}
-
 // slices of the two-stage reduction (tiles > 2048): enough (channel-block, slice) workgroups to cover the machine — C3D conv1 has
 // 50 176 tiles of ONE 64-channel block, and 64 slices left three quarters of the CUs idle (91 us per finalize)
 static int finalize_slices(int tiles) { return tiles >= 8192 ? 256 : (tiles >= 4096 ? 64 : (tiles >= 64 ? 16 : 1)); }
@@ -1208,22 +1179,6 @@ static int finalize_slices(int tiles) { return tiles >= 8192 ? 256 : (tiles >= 4
 size_t rsp_bn_finalize_workspace(int32_t tiles, int32_t C) {
   const int S = finalize_slices(tiles);
   return (size_t)S * C * 2 * sizeof(double);
-}
-
-int rsp_bn_finalize(const float* stat_partials, int32_t tiles, int32_t C, int32_t stat_ld, int64_t count, const float* conv_bias,
-                    const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                    float* running_var, float* mean_invstd, float* scale_shift, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-  return rsp_bn_finalize_v(stat_partials, tiles, C, C, stat_ld, count, conv_bias, gamma, beta, eps, momentum, running_mean, running_var,
-                           mean_invstd, scale_shift, workspace, workspace_bytes, stream);
-}
-
-int rsp_bn_finalize_v(const float* stat_partials, int32_t tiles, int32_t C, int32_t c_valid, int32_t stat_ld, int64_t count,
-                      const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                      float* running_var, float* mean_invstd, float* scale_shift, void* workspace,
-                      size_t workspace_bytes, void* stream) {
-  return rsp_bn_finalize_x(stat_partials, tiles, C, c_valid, stat_ld, count, conv_bias, gamma, beta, eps, momentum, running_mean,
-                           running_var, nullptr, mean_invstd, scale_shift, workspace, workspace_bytes, stream);
 }
 
 // EMA of the running statistics for a list of BatchNorm layers in one launch (jobs in device memory): what rsp_bn_finalize does
@@ -1242,10 +1197,10 @@ int rsp_bn_running_update(const rsp_bn_ema_job* jobs_device, int32_t n_jobs, int
   return rsp_check_launch("bn_ema_kernel");
 }
 
-int rsp_bn_finalize_x(const float* stat_partials, int32_t tiles, int32_t C, int32_t c_valid, int32_t stat_ld, int64_t count,
-                      const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                      float* running_var, float* batch_stats_out, float* mean_invstd, float* scale_shift, void* workspace,
-                      size_t workspace_bytes, void* stream) {
+int rsp_bn_finalize(const float* stat_partials, int32_t tiles, int32_t C, int32_t c_valid, int32_t stat_ld, int64_t count,
+                    const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
+                    float* running_var, float* batch_stats_out, float* mean_invstd, float* scale_shift, void* workspace,
+                    size_t workspace_bytes, void* stream) {
   RSP_REQUIRE(stat_partials && mean_invstd && scale_shift && workspace, "rsp_bn_finalize: null pointer");
   RSP_REQUIRE(tiles > 0 && C > 0 && count > 0 && stat_ld >= C && c_valid > 0 && c_valid <= C, "rsp_bn_finalize: bad size");
   const int S = finalize_slices(tiles);
@@ -1269,12 +1224,7 @@ int rsp_bn_finalize_x(const float* stat_partials, int32_t tiles, int32_t C, int3
 }
 
 int rsp_bn_act_pool_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, const float* residual,
-                        int relu, float* out, void* stream) {
-  return rsp_bn_act_pool_gate_fwd(d, y, scale_shift, residual, relu, nullptr, out, stream);
-}
-
-int rsp_bn_act_pool_gate_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, const float* residual,
-                             int relu, const float* gate, float* out, void* stream) {
+                        int relu, const float* gate, float* out, void* stream) {
   RSP_REQUIRE(pool_ok(d, false), "rsp_bn_act_pool_fwd: bad descriptor");
   RSP_REQUIRE(y && scale_shift && out, "rsp_bn_act_pool_fwd: null pointer");
   // overlapping 3x3x3 / 1x3x3 windows without residual (the ResNet stems; S3D-G's gated front-end units): the pooling body with the apply folded
@@ -1282,7 +1232,7 @@ int rsp_bn_act_pool_gate_fwd(const rsp_pool3d_desc* d, const float* y, const flo
   if (!residual && (d->kT != d->sT || d->kH != d->sH || d->kW != d->sW || d->pT || d->pH || d->pW) &&
       rsp_bn_act_maxpool_applicable(d) && rsp_aligned16(y) && rsp_aligned16(out) && rsp_aligned16(scale_shift) &&
       (!gate || rsp_aligned16(gate)))
-    return rsp_bn_act_maxpool_gate_fwd(d, y, scale_shift, relu, gate, out, nullptr, stream);
+    return rsp_bn_act_maxpool_fwd(d, y, scale_shift, relu, gate, out, nullptr, stream);
   PoolParams p;
   p.d = *d; p.y = y; p.ss = scale_shift; p.res = residual; p.gate = gate; p.out = out; p.relu = relu;
   const bool vec = d->C % 4 == 0 && d->in_ld % 4 == 0 && d->out_ld % 4 == 0 && rsp_aligned16(y) && rsp_aligned16(out) &&
@@ -1291,7 +1241,7 @@ int rsp_bn_act_pool_gate_fwd(const rsp_pool3d_desc* d, const float* y, const flo
   p.cg = vec ? d->C / 4 : d->C;
   const Layout L = make_layout(d, p.cg, 4);
   RSP_REQUIRE(L.npos < (1ll << 31), "rsp_bn_act_pool_fwd: more than 2^31 - 1 output positions");
-  p.cgc = L.cgc; p.ppi = L.ppi; p.npos = L.npos; p.dcgc = L.dcgc; p.dWo = L.dWo; p.dHo = L.dHo; p.dDo = L.dDo;
+  set_layout(p, L);
   RSP_BN_LAUNCH(bn_act_pool_fwd_kernel, vec, bn_mode(d, gate != nullptr), L.grid, (hipStream_t)stream, p);
   return rsp_check_launch("bn_act_pool_fwd_kernel");
 }
@@ -1303,24 +1253,8 @@ size_t rsp_bn_bwd_workspace(const rsp_pool3d_desc* d) {
 
 int rsp_bn_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
                         const float* gamma, const float* mean_invstd, const float* scale_shift, int relu, float* dy,
-                        float* dres, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
-                        void* stream) {
-  return rsp_bn_act_pool_bwd_v(d, y, residual, dout, gamma, mean_invstd, scale_shift, relu, dy, dres, dgamma, dbeta, d ? d->C : 0,
-                               workspace, workspace_bytes, stream);
-}
-
-int rsp_bn_act_pool_bwd_v(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
-                          const float* gamma, const float* mean_invstd, const float* scale_shift, int relu, float* dy,
-                          float* dres, float* dgamma, float* dbeta, int32_t c_valid, void* workspace, size_t workspace_bytes,
-                          void* stream) {
-  return rsp_bn_act_pool_bwd_g(d, y, residual, dout, gamma, mean_invstd, scale_shift, relu, dy, dres, dgamma, dbeta, c_valid, nullptr,
-                               nullptr, workspace, workspace_bytes, stream);
-}
-
-int rsp_bn_act_pool_bwd_g(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
-                          const float* gamma, const float* mean_invstd, const float* scale_shift, int relu, float* dy,
-                          float* dres, float* dgamma, float* dbeta, int32_t c_valid, const float* gate, const float* dmean,
-                          void* workspace, size_t workspace_bytes, void* stream) {
+                        float* dres, float* dgamma, float* dbeta, int32_t c_valid, const float* gate, const float* dmean,
+                        void* workspace, size_t workspace_bytes, void* stream) {
   RSP_REQUIRE(pool_ok(d, true), "rsp_bn_act_pool_bwd: needs disjoint windows (kernel == stride, no padding)");
   RSP_REQUIRE(!gate || (dmean && d->kT * d->kH * d->kW == 1 && d->sT * d->sH * d->sW == 1 && !residual),
               "rsp_bn_act_pool_bwd: a gated unit has a unit window, no residual, and needs dmean");
@@ -1351,7 +1285,7 @@ int rsp_bn_act_pool_bwd_g(const rsp_pool3d_desc* d, const float* y, const float*
   p.sums = sums;
   const Layout L = make_layout(d, p.cg, 4);
   RSP_REQUIRE(L.npos < (1ll << 31), "rsp_bn_act_pool_bwd: more than 2^31 - 1 output positions");
-  p.cgc = L.cgc; p.ppi = L.ppi; p.npos = L.npos; p.dcgc = L.dcgc; p.dWo = L.dWo; p.dHo = L.dHo; p.dDo = L.dDo;
+  set_layout(p, L);
   p.nblocks = reduce_blocks(d, p.cg);
   dim3 rgrid(p.nblocks, rsp_cdiv(p.cg, 256));
   const int mode = bn_mode(d, gate != nullptr);

@@ -868,7 +868,7 @@ size_t rsp_conv3d_wgrad_workspace(const rsp_conv3d_desc* d) {
 }
 
 static int wgrad_all(const rsp_conv3d_desc* d, const float* x, const float* dy, float* dw_ref, float* dbias, int cout_valid,
-                     int cin_valid, void* workspace, size_t workspace_bytes, void* stream, const uint2* ext_rowgeom = nullptr) {
+                     int cin_valid, void* workspace, size_t workspace_bytes, void* stream, const uint2* ext_rowgeom) {
   rsp_note_reset();
   // problems over disjoint output-channel ranges; dy keeps its row pitch (out_ld), dw / dbias are contiguous per channel
   const WSegs g = wgrad_segments(d);
@@ -887,23 +887,6 @@ static int wgrad_all(const rsp_conv3d_desc* d, const float* x, const float* dy, 
   return RSP_OK;
 }
 
-int rsp_conv3d_wgrad(const rsp_conv3d_desc* d, const float* x, const float* dy, float* dw_ref, float* dbias,
-                     void* workspace, size_t workspace_bytes, void* stream) {
-  RSP_REQUIRE(wdesc_ok(d), "rsp_conv3d_wgrad: bad descriptor");
-  RSP_REQUIRE(x && dy && dw_ref && workspace, "rsp_conv3d_wgrad: null pointer");
-  RSP_REQUIRE(rsp_aligned16(workspace), "rsp_conv3d_wgrad: workspace must be 16-byte aligned");
-  return wgrad_all(d, x, dy, dw_ref, dbias, d->Cout, d->Cin, workspace, workspace_bytes, stream);
-}
-
-int rsp_conv3d_wgrad_v(const rsp_conv3d_desc* d, const float* x, const float* dy, float* dw_ref, int32_t cout_valid,
-                       int32_t cin_valid, void* workspace, size_t workspace_bytes, void* stream) {
-  RSP_REQUIRE(wdesc_ok(d), "rsp_conv3d_wgrad_v: bad descriptor");
-  RSP_REQUIRE(x && dy && dw_ref && workspace, "rsp_conv3d_wgrad_v: null pointer");
-  RSP_REQUIRE(rsp_aligned16(workspace), "rsp_conv3d_wgrad_v: workspace must be 16-byte aligned");
-  RSP_REQUIRE(cout_valid > 0 && cout_valid <= d->Cout && cin_valid > 0 && cin_valid <= d->Cin, "rsp_conv3d_wgrad_v: bad valid channel counts");
-  return wgrad_all(d, x, dy, dw_ref, nullptr, cout_valid, cin_valid, workspace, workspace_bytes, stream);
-}
-
 // Row-geometry table of a convolution (input byte offset + validity bits per output position; depends on the geometry only, not on
 // channels or data): a caller that keeps it per geometry saves the pre-pass launch of every weight-gradient call.
 size_t rsp_conv3d_rowgeom_bytes(const rsp_conv3d_desc* d) {
@@ -917,13 +900,13 @@ int rsp_conv3d_rowgeom(const rsp_conv3d_desc* d, void* table, void* stream) {
   return rowgeom_fill(d, table, (hipStream_t)stream);
 }
 
-int rsp_conv3d_wgrad_t(const rsp_conv3d_desc* d, const float* x, const float* dy, float* dw_ref, float* dbias, int32_t cout_valid,
-                       int32_t cin_valid, const void* rowgeom_table, void* workspace, size_t workspace_bytes, void* stream) {
-  RSP_REQUIRE(wdesc_ok(d), "rsp_conv3d_wgrad_t: bad descriptor");
-  RSP_REQUIRE(x && dy && dw_ref && workspace, "rsp_conv3d_wgrad_t: null pointer");
-  RSP_REQUIRE(rsp_aligned16(workspace) && (!rowgeom_table || rsp_aligned16(rowgeom_table)), "rsp_conv3d_wgrad_t: workspace / table must be 16-byte aligned");
-  RSP_REQUIRE(cout_valid > 0 && cout_valid <= d->Cout && cin_valid > 0 && cin_valid <= d->Cin, "rsp_conv3d_wgrad_t: bad valid channel counts");
-  RSP_REQUIRE(!dbias || (cout_valid == d->Cout && cin_valid == d->Cin), "rsp_conv3d_wgrad_t: a bias gradient needs unpadded channels");
+int rsp_conv3d_wgrad(const rsp_conv3d_desc* d, const float* x, const float* dy, float* dw_ref, float* dbias, int32_t cout_valid,
+                     int32_t cin_valid, const void* rowgeom_table, void* workspace, size_t workspace_bytes, void* stream) {
+  RSP_REQUIRE(wdesc_ok(d), "rsp_conv3d_wgrad: bad descriptor");
+  RSP_REQUIRE(x && dy && dw_ref && workspace, "rsp_conv3d_wgrad: null pointer");
+  RSP_REQUIRE(rsp_aligned16(workspace) && (!rowgeom_table || rsp_aligned16(rowgeom_table)), "rsp_conv3d_wgrad: workspace / table must be 16-byte aligned");
+  RSP_REQUIRE(cout_valid > 0 && cout_valid <= d->Cout && cin_valid > 0 && cin_valid <= d->Cin, "rsp_conv3d_wgrad: bad valid channel counts");
+  RSP_REQUIRE(!dbias || (cout_valid == d->Cout && cin_valid == d->Cin), "rsp_conv3d_wgrad: a bias gradient needs unpadded channels");
   return wgrad_all(d, x, dy, dw_ref, dbias, cout_valid, cin_valid, workspace, workspace_bytes, stream,
                    reinterpret_cast<const uint2*>(rowgeom_table));
 }
@@ -991,18 +974,15 @@ int wgrad_one(const rsp_conv3d_desc* d, const float* x, const float* dy, float* 
              (unsigned long long)p.M * sizeof(uint2) < (1ull << 32);   // row-geometry table addressed with 32-bit offsets
   int rc;
   if (dma) {
-    RowGeomParams g;
-    g.out = reinterpret_cast<uint2*>(workspace);
-    g.M = p.M; g.Gd = p.Gd; g.Gh = p.Gh; g.Gw = p.Gw; g.Di = p.Di; g.Hi = p.Hi; g.Wi = p.Wi; g.in_ld = p.in_ld;
-    g.sD = p.sD; g.sH = p.sH; g.sW = p.sW; g.kT = p.kT; g.kH = p.kH; g.kW = p.kW; g.pT = p.pT; g.pH = p.pH; g.pW = p.pW;
     if (ext_rowgeom) {       // the caller keeps the table of this geometry (rsp_conv3d_rowgeom): nothing to compute per call
-      g.out = const_cast<uint2*>(ext_rowgeom);
-    } else if (!rowgeom_ready) {    // the table depends on the rows only: the output-channel segments of one call share it
-      hipLaunchKernelGGL(rowgeom_kernel, dim3(rsp_cdiv(p.M, 256)), dim3(256), 0, s, g);
-      rc = rsp_check_launch("rowgeom_kernel");
-      if (rc != RSP_OK) return rc;
+      p.rowgeom = ext_rowgeom;
+    } else {
+      if (!rowgeom_ready) {    // the table depends on the rows only: the output-channel segments of one call share it
+        rc = rowgeom_fill(d, workspace, s);
+        if (rc != RSP_OK) return rc;
+      }
+      p.rowgeom = reinterpret_cast<const uint2*>(workspace);
     }
-    p.rowgeom = g.out;
   }
   if (dma && w.bm == 32) rc = w.h16 ? launch_w_dma_h16(p, s) : launch_w_dma<32, 128, 1, 4>(p, s);
   else if (w.bm == 32) rc = launch_w_vec<32, 128, 1, 4>(p, va, vb, s);

@@ -41,5 +41,5 @@ const char* rsp_strerror(int code) {
     default: return "unknown error";
   }
 }
-int rsp_version(void) { return 120; }
+int rsp_version(void) { return 130; }
 }

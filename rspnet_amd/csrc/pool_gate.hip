@@ -766,8 +766,8 @@ int rsp_bn_act_maxpool_applicable(const rsp_pool3d_desc* d) {
          (long long)d->N * d->Do * d->Ho * d->Wo * (d->C / 4) < (1ll << 31);
 }
 
-int rsp_bn_act_maxpool_gate_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, int relu, const float* gate, float* out,
-                                int32_t* argmax, void* stream) {
+int rsp_bn_act_maxpool_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, int relu, const float* gate, float* out,
+                           int32_t* argmax, void* stream) {
   RSP_REQUIRE(rsp_bn_act_maxpool_applicable(d), "rsp_bn_act_maxpool_fwd: 3x3x3 / 1x3x3 windows, channels and pitches multiples of 4");
   RSP_REQUIRE(y && scale_shift && out, "rsp_bn_act_maxpool_fwd: null pointer");
   RSP_REQUIRE(rsp_aligned16(y) && rsp_aligned16(out) && rsp_aligned16(scale_shift) && (!argmax || rsp_aligned16(argmax)) &&
@@ -786,11 +786,6 @@ int rsp_bn_act_maxpool_gate_fwd(const rsp_pool3d_desc* d, const float* y, const 
     else hipLaunchKernelGGL((bn_maxpool_fwd_vec_kernel<false, 1, 3, 3>), grid, dim3(256), 0, st, p, scale_shift, relu, gate);
   }
   return rsp_check_launch("bn_maxpool_fwd_vec_kernel");
-}
-
-int rsp_bn_act_maxpool_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, int relu, float* out, int32_t* argmax,
-                           void* stream) {
-  return rsp_bn_act_maxpool_gate_fwd(d, y, scale_shift, relu, nullptr, out, argmax, stream);
 }
 
 int rsp_maxpool3d_bwd(const rsp_pool3d_desc* d, const float* dout, const int32_t* argmax, float* dx, void* stream) {
@@ -933,7 +928,7 @@ int rsp_gate_bwd(const float* x, const float* dout, int32_t N, int32_t P, int32_
 
 // Parameter half of the gating backward for a unit whose forward kept no activation (rsp_bn_gate_sums with act == NULL): the
 // activation is recomputed from y.  Writes dw, db and dmean ([N][C], = d loss / d sum_p a before the 1/P) for
-// rsp_bn_act_pool_bwd_g, which folds the data half (dx = dout*gate + dmean/P) into the BatchNorm backward in front of it.
+// rsp_bn_act_pool_bwd, which folds the data half (dx = dout*gate + dmean/P) into the BatchNorm backward in front of it.
 int rsp_gate_bwd_params(const float* y, const float* scale_shift, int relu, const float* dout, int32_t N, int32_t P, int32_t C,
                         int32_t y_ld, int32_t dout_ld, const float* w, const float* mean, const float* gate, float* dw, float* db,
                         float* dmean, void* workspace, size_t workspace_bytes, void* stream) {

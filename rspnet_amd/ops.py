@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import functools
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -82,11 +83,8 @@ class PoolGeom:
                              in_ld or self.C, out_ld or self.C, res_ld or self.C)
 
 
-import functools
-
-
 @functools.lru_cache(maxsize=4096)
-def _conv_plan(lib_id, g: "ConvGeom", in_ld, out_ld):
+def _conv_plan(g: "ConvGeom", in_ld, out_ld):
     """ctypes descriptor + geometry-derived sizes of one conv application, built once per distinct geometry (the
     per-launch host cost matters for the small-layer backbones: ~700-2500 launches per step).  Names and workspace sizes are read
     off the plan the library's launch path executes (conv_igemm.hip plan_conv): one decision, not a second derivation."""
@@ -120,7 +118,7 @@ def _pack_signature(g: "ConvGeom", which: int, cout_src: int, cin_src: int):
 
 
 @functools.lru_cache(maxsize=4096)
-def _pool_plan(lib_id, pg: "PoolGeom", in_ld, out_ld, res_ld):
+def _pool_plan(pg: "PoolGeom", in_ld, out_ld, res_ld):
     lib = _lib.load()
     d = pg.desc(in_ld=in_ld, out_ld=out_ld, res_ld=res_ld)
     ref = C.byref(d)
@@ -168,6 +166,18 @@ def _rows_ld(t: torch.Tensor, name: str) -> int:
     if not ok:
         raise _lib.RspError(f"{name}: expected a dense NDHWC tensor or a channel slice of one")
     return ld
+
+
+def _dy_target(y, in_ld: int, dy_out):
+    """Where a BatchNorm backward writes dy: dy_out when given (it must have y's shape and channel pitch), else a fresh tensor — which
+    a y that is a channel slice cannot have."""
+    if dy_out is not None:
+        if _rows_ld(dy_out, "dy_out") != in_ld or dy_out.shape != y.shape:
+            raise _lib.RspError("dy_out: expected the shape and channel pitch of y")
+        return dy_out
+    if not y.is_contiguous():
+        raise _lib.RspError("y is a channel slice: pass dy_out with the same pitch")
+    return torch.empty_like(y)
 
 
 class HipOps:
@@ -251,7 +261,7 @@ class HipOps:
     def conv_fwd(self, g: ConvGeom, x, w_packed, bias, want_stats: bool, out: Optional[torch.Tensor] = None,
                  out_ld: Optional[int] = None, in_ld: Optional[int] = None):
         _chk(x, "x")
-        d, dref, tiles, wsb, _, _, (do, ho, wo), names = _conv_plan(0, g, in_ld, out_ld)
+        d, dref, tiles, wsb, _, _, (do, ho, wo), names = _conv_plan(g, in_ld, out_ld)
         if out is None:
             out = torch.empty((g.N, do, ho, wo, g.Cout), dtype=torch.float32, device=x.device)
         stats = None
@@ -267,7 +277,7 @@ class HipOps:
     def conv_dgrad(self, g: ConvGeom, dy, w_ref):
         _chk(dy, "dy")
         _chk(w_ref, "w_ref")
-        d, dref, _, _, wsb, _, _, names = _conv_plan(0, g, None, None)
+        d, dref, _, _, wsb, _, _, names = _conv_plan(g, None, None)
         dx = torch.empty((g.N, g.Di, g.Hi, g.Wi, g.Cin), dtype=torch.float32, device=dy.device)
         ws = self._workspace(dy.device, wsb)
         e0 = self._ev()
@@ -279,7 +289,7 @@ class HipOps:
     def conv_dgrad_packed(self, g: ConvGeom, dy, w_packed):
         """dgrad over weights re-packed by a PackSet (which=1 entry)."""
         _chk(dy, "dy")
-        d, dref, _, _, wsb, _, _, names = _conv_plan(0, g, None, None)
+        d, dref, _, _, wsb, _, _, names = _conv_plan(g, None, None)
         dx = torch.empty((g.N, g.Di, g.Hi, g.Wi, g.Cin), dtype=torch.float32, device=dy.device)
         ws = self._workspace(dy.device, wsb)
         e0 = self._ev()
@@ -304,15 +314,15 @@ class HipOps:
         _chk(x, "x")
         _chk(dw_out, "dw_out")
         dy_ld = _rows_ld(dy, "dy")                # dy may be a channel slice of a wider gradient tensor
-        d, dref, _, _, _, wsb, _, names = _conv_plan(0, g, None, None if dy_ld == g.Cout else dy_ld)
+        d, dref, _, _, _, wsb, _, names = _conv_plan(g, None, None if dy_ld == g.Cout else dy_ld)
         ws = self._workspace(x.device, wsb)
         if dw_out.shape[0] > g.Cout or dw_out.shape[1] > g.Cin or (dbias_out is not None and tuple(dw_out.shape[:2]) != (g.Cout, g.Cin)):
             raise _lib.RspError("conv_wgrad: dw_out has more channels than the geometry, or a bias gradient with padded channels")
         table = self._rowgeom_table(g, d, dref, x.device)
         e0 = self._ev()
         # (a geometry with zero-padded channels the parameter does not have: their gradients are dropped by the reduce)
-        _lib.check(self.lib.rsp_conv3d_wgrad_t(dref, _ptr(x), _ptr(dy), _ptr(dw_out), _ptr(dbias_out), dw_out.shape[0], dw_out.shape[1],
-                                               _ptr(table), _ptr(ws), wsb, _stream()), "rsp_conv3d_wgrad_t")
+        _lib.check(self.lib.rsp_conv3d_wgrad(dref, _ptr(x), _ptr(dy), _ptr(dw_out), _ptr(dbias_out), dw_out.shape[0], dw_out.shape[1],
+                                             _ptr(table), _ptr(ws), wsb, _stream()), "rsp_conv3d_wgrad")
         self._log("conv_wgrad", g, e0, names[2])
 
     ROWGEOM_MAX_TABLES = 128
@@ -390,9 +400,9 @@ class HipOps:
         ws = self._workspace(stats.device, wsb)
         # the parameter vectors may be shorter than the convolution's (zero-padded) channel count: gamma's length says how many
         c_valid = Cc if gamma is None else int(gamma.shape[0])
-        _lib.check(self.lib.rsp_bn_finalize_x(_ptr(stats), tiles, Cc, c_valid, stat_ld, count, _ptr(conv_bias), _ptr(gamma), _ptr(beta),
-                                              eps, momentum, _ptr(running_mean), _ptr(running_var), _ptr(batch_stats_out), _ptr(mi),
-                                              _ptr(ss), _ptr(ws), wsb, _stream()), "rsp_bn_finalize")
+        _lib.check(self.lib.rsp_bn_finalize(_ptr(stats), tiles, Cc, c_valid, stat_ld, count, _ptr(conv_bias), _ptr(gamma), _ptr(beta),
+                                            eps, momentum, _ptr(running_mean), _ptr(running_var), _ptr(batch_stats_out), _ptr(mi),
+                                            _ptr(ss), _ptr(ws), wsb, _stream()), "rsp_bn_finalize")
         return mi, ss
 
     def bn_ema_set(self, entries):
@@ -405,9 +415,9 @@ class HipOps:
         if out is None:
             do, ho, wo = pg.out_dims
             out = torch.empty((pg.N, do, ho, wo, pg.C), dtype=torch.float32, device=y.device)
-        d, dref, _, _ = _pool_plan(0, pg, in_ld, _rows_ld(out, "out"), None if residual is None else _rows_ld(residual, "residual"))
+        d, dref, _, _ = _pool_plan(pg, in_ld, _rows_ld(out, "out"), None if residual is None else _rows_ld(residual, "residual"))
         e0 = self._ev()
-        _lib.check(self.lib.rsp_bn_act_pool_fwd(dref, _ptr(y), _ptr(scale_shift), _ptr(residual), int(relu), _ptr(out),
+        _lib.check(self.lib.rsp_bn_act_pool_fwd(dref, _ptr(y), _ptr(scale_shift), _ptr(residual), int(relu), None, _ptr(out),
                                                 _stream()), "rsp_bn_act_pool_fwd")
         n_in = pg.N * pg.Di * pg.Hi * pg.Wi * pg.C
         self._log_hbm("bn_act_pool_fwd", 4 * (n_in * (1 if residual is None else 2) + out.numel()), e0)
@@ -425,8 +435,8 @@ class HipOps:
         out = torch.empty((pg.N, do, ho, wo, pg.C), dtype=torch.float32, device=y.device)
         idx = torch.empty((pg.N, do, ho, wo, pg.C), dtype=torch.int32, device=y.device) if keep else None
         e0 = self._ev()
-        _lib.check(self.lib.rsp_bn_act_maxpool_fwd(C.byref(d), _ptr(y), _ptr(scale_shift), int(relu), _ptr(out), _ptr(idx), _stream()),
-                   "rsp_bn_act_maxpool_fwd")
+        _lib.check(self.lib.rsp_bn_act_maxpool_fwd(C.byref(d), _ptr(y), _ptr(scale_shift), int(relu), None, _ptr(out), _ptr(idx),
+                                                   _stream()), "rsp_bn_act_maxpool_fwd")
         self._log_hbm("bn_act_pool_fwd", 4 * (pg.N * pg.Di * pg.Hi * pg.Wi * pg.C + out.numel() * (2 if keep else 1)), e0)
         return out, idx
 
@@ -434,22 +444,15 @@ class HipOps:
                         want_dres: bool, dgamma_out, dbeta_out, dy_out=None):
         """dy_out: where to write dy (same channel pitch as y — a slice of a wider gradient tensor when y is a slice)."""
         in_ld = _rows_ld(y, "y")
-        d, dref, wsb, _ = _pool_plan(0, pg, in_ld, _rows_ld(dout, "dout"), None if residual is None else _rows_ld(residual, "residual"))
-        if dy_out is not None:
-            if _rows_ld(dy_out, "dy_out") != in_ld or dy_out.shape != y.shape:
-                raise _lib.RspError("dy_out: expected the shape and channel pitch of y")
-            dy = dy_out
-        else:
-            if not y.is_contiguous():
-                raise _lib.RspError("y is a channel slice: pass dy_out with the same pitch")
-            dy = torch.empty_like(y)
+        d, dref, wsb, _ = _pool_plan(pg, in_ld, _rows_ld(dout, "dout"), None if residual is None else _rows_ld(residual, "residual"))
+        dy = _dy_target(y, in_ld, dy_out)
         dres = torch.empty_like(y) if want_dres else None
         ws = self._workspace(y.device, wsb)
         c_valid = pg.C if gamma is None else int(gamma.shape[0])      # < C: zero-padded channels (gamma / dgamma / dbeta are short)
         e0 = self._ev()
-        _lib.check(self.lib.rsp_bn_act_pool_bwd_v(dref, _ptr(y), _ptr(residual), _ptr(dout), _ptr(gamma),
-                                                  _ptr(mean_invstd), _ptr(scale_shift), int(relu), _ptr(dy), _ptr(dres),
-                                                  _ptr(dgamma_out), _ptr(dbeta_out), c_valid, _ptr(ws), wsb, _stream()),
+        _lib.check(self.lib.rsp_bn_act_pool_bwd(dref, _ptr(y), _ptr(residual), _ptr(dout), _ptr(gamma),
+                                                _ptr(mean_invstd), _ptr(scale_shift), int(relu), _ptr(dy), _ptr(dres),
+                                                _ptr(dgamma_out), _ptr(dbeta_out), c_valid, None, None, _ptr(ws), wsb, _stream()),
                    "rsp_bn_act_pool_bwd")
         # reduce pass: y (+ residual) + dout read; apply pass: the same again, dy (+ dres) written
         n_in = y.numel()
@@ -463,15 +466,8 @@ class HipOps:
         forward applied; mean_invstd holds running_mean - conv_bias and rsqrt(running_var + eps).  dgamma_out / dbeta_out may be
         shorter than C (zero-padded channels: dy = 0 there).  dy_out as in bn_act_pool_bwd."""
         in_ld = _rows_ld(y, "y")
-        d, dref, _, _ = _pool_plan(0, pg, in_ld, _rows_ld(dout, "dout"), None if residual is None else _rows_ld(residual, "residual"))
-        if dy_out is not None:
-            if _rows_ld(dy_out, "dy_out") != in_ld or dy_out.shape != y.shape:
-                raise _lib.RspError("dy_out: expected the shape and channel pitch of y")
-            dy = dy_out
-        else:
-            if not y.is_contiguous():
-                raise _lib.RspError("y is a channel slice: pass dy_out with the same pitch")
-            dy = torch.empty_like(y)
+        d, dref, _, _ = _pool_plan(pg, in_ld, _rows_ld(dout, "dout"), None if residual is None else _rows_ld(residual, "residual"))
+        dy = _dy_target(y, in_ld, dy_out)
         if want_dres and residual is None:
             raise _lib.RspError("want_dres without a residual")
         dres = torch.empty(y.shape, dtype=torch.float32, device=y.device) if want_dres else None
@@ -552,15 +548,15 @@ class HipOps:
         elif pool_idx:
             # the pooled form for a forward a backward follows: the max-pool's arg-max written by the same pass (returned fifth);
             # the caller has checked bn_act_gate_pool_idx_ok
-            d, dref, _, _ = _pool_plan(0, og, y_ld, _rows_ld(out, "out"), None)
+            d, dref, _, _ = _pool_plan(og, y_ld, _rows_ld(out, "out"), None)
             idx = torch.empty(tuple(out.shape), dtype=torch.int32, device=y.device)
-            _lib.check(self.lib.rsp_bn_act_maxpool_gate_fwd(dref, _ptr(y), _ptr(scale_shift), int(relu), _ptr(gate), _ptr(out), _ptr(idx),
-                                                            _stream()), "rsp_bn_act_maxpool_gate_fwd")
+            _lib.check(self.lib.rsp_bn_act_maxpool_fwd(dref, _ptr(y), _ptr(scale_shift), int(relu), _ptr(gate), _ptr(out), _ptr(idx),
+                                                       _stream()), "rsp_bn_act_maxpool_fwd")
             return out, a, mean, gate, idx
         else:
-            d, dref, _, _ = _pool_plan(0, og, y_ld, _rows_ld(out, "out"), None)
-            _lib.check(self.lib.rsp_bn_act_pool_gate_fwd(dref, _ptr(y), _ptr(scale_shift), None, int(relu), _ptr(gate), _ptr(out),
-                                                         _stream()), "rsp_bn_act_pool_gate_fwd")
+            d, dref, _, _ = _pool_plan(og, y_ld, _rows_ld(out, "out"), None)
+            _lib.check(self.lib.rsp_bn_act_pool_fwd(dref, _ptr(y), _ptr(scale_shift), None, int(relu), _ptr(gate), _ptr(out),
+                                                    _stream()), "rsp_bn_act_pool_fwd")
         return out, a, mean, gate
 
     def bn_act_gate_pool_idx_ok(self, pool: PoolGeom, y, scale_shift) -> bool:
@@ -583,13 +579,13 @@ class HipOps:
         _lib.check(self.lib.rsp_gate_bwd_params(_ptr(y), _ptr(scale_shift), int(relu), _ptr(dout), N, P, Cc, Cc, dout_ld, _ptr(_chk(w, "w")),
                                                 _ptr(mean), _ptr(gate), _ptr(dw_out), _ptr(db_out), _ptr(dmean), _ptr(ws), wsb,
                                                 _stream()), "rsp_gate_bwd_params")
-        d, dref, wsb2, _ = _pool_plan(0, pg, Cc, dout_ld, None)
+        d, dref, wsb2, _ = _pool_plan(pg, Cc, dout_ld, None)
         ws2 = self._workspace(y.device, wsb2)
         dy = torch.empty_like(y)
         c_valid = pg.C if gamma is None else int(gamma.shape[0])
-        _lib.check(self.lib.rsp_bn_act_pool_bwd_g(dref, _ptr(y), None, _ptr(dout), _ptr(gamma), _ptr(mean_invstd), _ptr(scale_shift),
-                                                  int(relu), _ptr(dy), None, _ptr(dgamma_out), _ptr(dbeta_out), c_valid, _ptr(gate),
-                                                  _ptr(dmean), _ptr(ws2), wsb2, _stream()), "rsp_bn_act_pool_bwd_g")
+        _lib.check(self.lib.rsp_bn_act_pool_bwd(dref, _ptr(y), None, _ptr(dout), _ptr(gamma), _ptr(mean_invstd), _ptr(scale_shift),
+                                                int(relu), _ptr(dy), None, _ptr(dgamma_out), _ptr(dbeta_out), c_valid, _ptr(gate),
+                                                _ptr(dmean), _ptr(ws2), wsb2, _stream()), "rsp_bn_act_pool_bwd")
         return dy
 
     def gate_bwd(self, x, dout, w, mean, gate, dw_out, db_out):

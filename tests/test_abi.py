@@ -38,6 +38,48 @@ def test_geometry_queries_without_gpu():
     assert b"descriptor" in lib.rsp_last_error()
 
 
+# the ten names version 120 exported and 130 does not, spelled stem + retired suffix: a search of the tree for a retired name finds nothing
+RETIRED = [stem + suffix for stem, suffixes in (
+    ("rsp_bn_finalize", ("_v", "_x")), ("rsp_bn_act_pool_bwd", ("_v", "_g")), ("rsp_conv3d_wgrad", ("_v", "_t")),
+    ("rsp_bn_act_pool", ("_gate_fwd",)), ("rsp_bn_act_maxpool", ("_gate_fwd",)), ("rsp_bn_stat", ("s", "_tiles"))) for suffix in suffixes]
+
+
+def test_version_130_has_one_entry_point_per_operation():
+    """rsp_version() 130 folded the suffixed variants into the plain names: none of the old symbols is exported any more."""
+    lib = _lib.load()
+    assert lib.rsp_version() == 130
+    assert len(RETIRED) == 10
+    for name in RETIRED:
+        assert not hasattr(lib, name), name
+        assert name not in _lib.SIGNATURES
+
+
+def test_folded_entry_points_reject_bad_arguments_before_any_launch():
+    """The union of the argument checks of the former variants, through the one entry point each operation has now: RSP_EINVAL
+    with the plain name in rsp_last_error(), on dummy pointers (nothing is dereferenced, nothing is launched)."""
+    lib = _lib.load()
+    P = ctypes.c_void_p(1 << 20)      # non-null, 16-byte aligned, never touched
+    Cin, Cout = 8, 12
+    d = _lib.ConvDesc(2, 4, 6, 6, Cin, 4, 6, 6, Cout, 3, 3, 3, 1, 1, 1, 1, 1, 1, Cin, Cout)
+    wgrad = lambda dbias, cov, civ: lib.rsp_conv3d_wgrad(ctypes.byref(d), P, P, P, dbias, cov, civ, None, P, 1 << 30, None)
+    for args, what in (((None, 0, Cin), b"valid channel counts"), ((None, Cout + 1, Cin), b"valid channel counts"),
+                       ((P, Cout, Cin - 1), b"bias gradient")):
+        assert wgrad(*args) == -1, args
+        err = lib.rsp_last_error()
+        assert err.startswith(b"rsp_conv3d_wgrad: ") and what in err, err
+    C_ = 16
+    pd = _lib.PoolDesc(2, 4, 6, 6, C_, 4, 6, 6, 1, 1, 1, 1, 1, 1, 0, 0, 0, C_, C_, C_)
+    bwd = lambda c_valid, gate, dmean: lib.rsp_bn_act_pool_bwd(ctypes.byref(pd), P, None, P, P, P, P, 1, P, None, P, P, c_valid, gate,
+                                                                dmean, P, 1 << 30, None)
+    for args, what in (((C_, P, None), b"needs dmean"), ((0, None, None), b"valid channel count")):
+        assert bwd(*args) == -1, args
+        err = lib.rsp_last_error()
+        assert err.startswith(b"rsp_bn_act_pool_bwd: ") and what in err, err
+    assert lib.rsp_bn_finalize(P, 4, C_, C_ + 1, C_, 288, None, P, P, 1e-5, 0.1, P, P, None, P, P, P, 1 << 30, None) == -1
+    err = lib.rsp_last_error()
+    assert err.startswith(b"rsp_bn_finalize: ") and b"bad size" in err, err
+
+
 def test_ops_fail_loudly_without_gpu_tensors():
     import pytest
     import torch

@@ -734,8 +734,8 @@ def test_packed_weights_are_shared_across_input_geometries(hip):
 
 def test_channel_padded_unit_uses_the_parameters_own_lengths(hip):
     """R(2+1)D's odd mid-channel counts (83 / 230 / 921, models/r2plus1d_vcop.py:35-38) run zero-padded to a multiple of 4; the
-    BatchNorm vectors and the weight gradient keep the parameter's own shape: rsp_bn_finalize_v / rsp_bn_act_pool_bwd_v /
-    rsp_conv3d_wgrad_v treat the padding as gamma = beta = 0 and drop its gradients (no staging copies in the engine)."""
+    BatchNorm vectors and the weight gradient keep the parameter's own shape: rsp_bn_finalize / rsp_bn_act_pool_bwd /
+    rsp_conv3d_wgrad (c_valid, cout_valid / cin_valid) treat the padding as gamma = beta = 0 and drop its gradients (no staging copies in the engine)."""
     N, D, H, W, Cin, Cv, Cp = 2, 4, 10, 10, 64, 83, 84
     g = ConvGeom(N, D, H, W, Cin, Cp, (1, 3, 3), (1, 1, 1), (0, 1, 1))
     x = rnd(N, D, H, W, Cin, seed=1)
@@ -784,7 +784,7 @@ def test_channel_padded_unit_uses_the_parameters_own_lengths(hip):
 
 @pytest.mark.parametrize("C,Cv,tiles", [(64, 64, 5), (84, 83, 3), (1152, 1152, 2), (128, 128, 3000)])
 def test_deferred_running_statistics_update(hip, C, Cv, tiles):
-    """rsp_bn_finalize_x with batch_stats_out reports the pass's batch moments and leaves the running statistics alone;
+    """rsp_bn_finalize with batch_stats_out reports the pass's batch moments and leaves the running statistics alone;
     rsp_bn_running_update (one launch for a list of layers) then moves them exactly as the in-place finalize does."""
     rows = tiles * 128 - 17
     part = (torch.rand(tiles, C, 2) + 0.5) * 100
@@ -971,3 +971,35 @@ def test_rowgeom_cache_is_bounded_and_ordered(hip):
         hip.ROWGEOM_MAX_TABLES = saved[0]
         hip._rowgeom.update(saved[1])
         hip._rowgeom_bytes = saved[2]
+
+
+def test_wgrad_without_a_kept_table_computes_its_own(hip):
+    """rsp_conv3d_wgrad with rowgeom_table == NULL fills the row-geometry table in a pre-pass of the call, in its workspace;
+    HipOps.conv_wgrad hands over the table it keeps per geometry.  Both must give the same bits: dw, and dbias where the channels are
+    unpadded.  Two tiny geometries (288 output rows, the smallest channel counts that land on each): 4 -> 4 channels run on a
+    table-streaming instance, 3 -> 4 (Cin % 4 != 0) on the one that decodes its rows itself; and the streaming one again with the
+    fourth output channel as padding (cout_valid = 3, no bias gradient)."""
+    import ctypes
+    from rspnet_amd.ops import _ptr, _stream
+    lib = hip.lib
+    for Cin, Cout, cov, streams in ((4, 4, 4, True), (3, 4, 4, False), (4, 4, 3, True)):
+        g = ConvGeom(2, 4, 6, 6, Cin, Cout, (3, 3, 3), (1, 1, 1), (1, 1, 1))
+        d = g.desc()
+        assert ("wgrad_dma" in lib.rsp_conv3d_kernel_name(ctypes.byref(d), 2).decode()) == streams
+        x = rnd(g.N, g.Di, g.Hi, g.Wi, Cin, seed=60 + Cin).to(DEV)
+        dy = rnd(g.N, *g.out_dims, Cout, seed=70 + Cin).to(DEV)
+        bias = cov == Cout
+        dw_kept = torch.empty(cov, Cin, 3, 3, 3, device=DEV)
+        db_kept = torch.empty(Cout, device=DEV) if bias else None
+        hip.conv_wgrad(g, x, dy, dw_kept, db_kept)
+        assert (x.device, g.N, g.Di, g.Hi, g.Wi, g.k, g.s, g.p, Cin) in hip._rowgeom       # the call above went through a kept table
+        dw_own = torch.full_like(dw_kept, float("nan"))
+        db_own = torch.full_like(db_kept, float("nan")) if bias else None
+        wsb = int(lib.rsp_conv3d_wgrad_workspace(ctypes.byref(d)))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+        rc = lib.rsp_conv3d_wgrad(ctypes.byref(d), _ptr(x), _ptr(dy), _ptr(dw_own), _ptr(db_own), cov, Cin, None, _ptr(ws), wsb, _stream())
+        assert rc == 0, lib.rsp_last_error()
+        torch.cuda.synchronize()
+        assert torch.equal(dw_own, dw_kept), (Cin, Cout, cov)
+        if bias:
+            assert torch.equal(db_own, db_kept), (Cin, Cout, cov)

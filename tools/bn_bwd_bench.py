@@ -3,7 +3,7 @@
 
     python tools/bn_bwd_bench.py [--blocks 7] [--iters 20] [--out profiles/bn_eval_bwd_bench.txt]
 
-The train-mode pair (rsp_bn_act_pool_bwd_v) is the yardstick: the one-pass op moves strictly fewer bytes, so on every geometry it
+The train-mode pair (rsp_bn_act_pool_bwd) is the yardstick: the one-pass op moves strictly fewer bytes, so on every geometry it
 must not be slower.  Geometries: the BatchNorm units of C3D conv2 .. conv5b and of R3D-18 layer1 .. layer4 at B = 32, 16 x 112^2
 clips.  The two ops alternate in blocks of `iters` calls (device events around each block); reported per op: the median block and
 the min-max over the blocks, achieved GB/s from the byte counts the ops log for the roofline pass (ops.HipOps._log_hbm), and the
