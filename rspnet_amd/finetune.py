@@ -14,19 +14,20 @@ order of tied entries unspecified.  That is the one divergence."""
 from __future__ import annotations
 
 import argparse
-import ctypes
-import json
 import logging
 import time
 from pathlib import Path
 from typing import Dict, Optional
 
-import numpy as np
 import torch
 import torch.distributed as dist
 from torch import Tensor, nn
 
 from . import _lib, ops
+from .framework.arguments import add_driver_arguments, parse_driver_args
+from .framework.driver import (append_scalars, finish_process_group, init_process_group, launch, load_config, load_states, save_run,
+                               seed_everything, setup_logging)
+from .framework.meters import DeviceMeters
 
 logger = logging.getLogger(__name__)
 BLACKLIST = ("fc.", "linear", "head", "new_fc", "fc8", "encoder_fuse")
@@ -82,59 +83,14 @@ def validate_step(model: nn.Module, criterion: nn.Module, clip: Tensor, target: 
 
 
 # ---- meters and criterion (finetune.py:101-143 behind the logits) ----------------------------------------------------------
-class Meters:
-    """The three running meters of an epoch context (loss, Acc@1, Acc@5; framework/meters/average.py) as ONE device struct,
-    rsp_cls_meters: val[3] / sum[3] fp32, count[3] int32.  FusedCrossEntropy updates it on the device; ``read`` is the only host
-    synchronisation."""
+class Meters(DeviceMeters):
+    """The three running meters of an epoch context (loss, Acc@1, Acc@5) over rsp_cls_meters; FusedCrossEntropy updates them on the
+    device."""
 
     NAMES = ("Loss", "Acc@1", "Acc@5")
     KEYS = ("loss", "acc1", "acc5")
     FMTS = (":f", ":6.2f", ":6.2f")
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        self.buf = torch.zeros(ctypes.sizeof(_lib.ClsMeters), dtype=torch.uint8, device=self.device)
-        self.val = self.buf[0:12].view(torch.float32)
-        self.sum = self.buf[12:24].view(torch.float32)
-        self.count = self.buf[24:36].view(torch.int32)
-
-    def reset(self):
-        self.buf.zero_()
-
-    @torch.no_grad()
-    def update(self, values, valid: int):
-        """AverageMeter.update(v_i, valid) for (loss, acc1[, acc5]) from torch ops -- the path without the HIP entry point."""
-        for i, v in enumerate(values):
-            v = v.detach().to(torch.float32).reshape(())
-            self.val[i] = v
-            self.sum[i] += v * valid
-            self.count[i] += valid
-
-    def read(self) -> Dict[str, Dict[str, float]]:
-        """{loss | acc1 | acc5: {val, avg, sum, count}}; avg = sum / count in fp32 (NaN while count is 0).  Synchronises."""
-        host = self.buf.cpu().numpy()
-        val, total, count = host[0:12].view(np.float32), host[12:24].view(np.float32), host[24:36].view(np.int32)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            avg = total / count.astype(np.float32)
-        return {k: {"val": float(val[i]), "avg": float(avg[i]), "sum": float(total[i]), "count": int(count[i])}
-                for i, k in enumerate(self.KEYS)}
-
-    def sync_distributed(self):
-        """All-reduce sum and count over the ranks (AverageMeter.sync_distributed); nothing to do on one rank."""
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            works = [dist.all_reduce(self.count, op=dist.ReduceOp.SUM, async_op=True),
-                     dist.all_reduce(self.sum, op=dist.ReduceOp.SUM, async_op=True)]
-            for w in works:
-                w.wait()
-
-    def pieces(self, stats=None):
-        """['Loss {val:f} ({avg:f})', 'Acc@1 {val:6.2f} ({avg:6.2f})', 'Acc@5 ...'] as AverageMeter.__str__ formats them."""
-        stats = stats or self.read()
-        return [("{name} {val" + fmt + "} ({avg" + fmt + "})").format(name=name, val=stats[k]["val"], avg=stats[k]["avg"])
-                for name, k, fmt in zip(self.NAMES, self.KEYS, self.FMTS)]
-
-    def __str__(self):
-        return "\t".join(self.pieces())
+    STRUCT = _lib.ClsMeters
 
 
 def rank_of_target(output: Tensor, target: Tensor) -> Tensor:
@@ -363,9 +319,7 @@ class Engine:
 
     # ---- checkpoints (finetune.py:259-310) ---------------------------------------------------------------------------
     def load_checkpoint(self, checkpoint_path):
-        states = torch.load(checkpoint_path, map_location=self.device, weights_only=False)
-        if states["arch"] != self.arch:
-            raise ValueError(f'Loading checkpoint arch {states["arch"]} does not match current arch {self.arch}')
+        states = load_states(checkpoint_path, self.device, self.arch)
         logger.info("Loading checkpoint from %s", checkpoint_path)
         self.model.module.load_state_dict(states["model"])
         logger.info("Checkpoint loaded")
@@ -428,14 +382,10 @@ class Engine:
         return stats["acc1"]["avg"]
 
     def _write_scalars(self, lr: float):
-        if self.scalars_path is None:
-            return
         rec = {"epoch": self.current_epoch, "train/lr": lr}
         for prefix, stats in (("train", self.train_stats), ("val", self.validate_stats)):
             rec.update({f"{prefix}/{k}": stats[k]["avg"] for k in Meters.KEYS})
-        self.scalars_path.parent.mkdir(parents=True, exist_ok=True)
-        with open(self.scalars_path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
+        append_scalars(self.scalars_path, rec)
 
     def run(self):
         num_epochs = 1 if getattr(self.args, "debug", False) else self.num_epochs
@@ -467,27 +417,12 @@ class Engine:
 
 # ---- command line (finetune.py:426-502) ------------------------------------------------------------------------------------
 def main_worker(local_rank: int, args, dist_url: str):
-    from .pretrain import _free_port, _merge, save_run_files
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO, format="%(asctime)s %(message)s")
-    if local_rank == 0:
-        Path(args.run_dir).mkdir(parents=True, exist_ok=True)
-        logging.getLogger().addHandler(logging.FileHandler(Path(args.run_dir) / "experiment.log"))
-    if args.seed is not None:
-        import random
-        random.seed(args.seed)
-        np.random.seed(args.seed)
-        torch.manual_seed(args.seed)
+    setup_logging(args, local_rank)
+    seed_everything(args.seed)
     torch.cuda.set_device(local_rank)
-    if args.world_size > 1:
-        dist.init_process_group("nccl", init_method=dist_url or f"tcp://127.0.0.1:{_free_port()}", rank=local_rank,
-                                world_size=args.world_size, device_id=torch.device("cuda", local_rank))
-    with open(args.config) as f:
-        cfg = json.load(f)
-    for snippet in args.ext_config or []:
-        _merge(cfg, json.loads(snippet))
-    if local_rank == 0:
-        Path(args.experiment_dir).mkdir(parents=True, exist_ok=True)
-        save_run_files(args, cfg)
+    group = init_process_group(args, local_rank, dist_url)
+    cfg = load_config(args.config, args.ext_config)
+    save_run(args, cfg, local_rank)
     if not args.validate:
         engine = Engine(args, cfg, local_rank=local_rank)
         if args.load_checkpoint is not None:
@@ -505,43 +440,21 @@ def main_worker(local_rank: int, args, dist_url: str):
     engine = Engine(args, cfg, local_rank=local_rank, final_validate=True)
     engine.load_checkpoint(validate_checkpoint)
     acc1 = engine.validate_epoch()
-    if args.world_size > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish_process_group(group)
     return acc1
 
 
 def parse_args(argv=None):
-    from .pretrain import resolve_continue, resolve_run_dir
-    ap = argparse.ArgumentParser(description="RSPNet action-recognition fine-tuning on MI355X (flag names follow the reference's "
-                                             "arguments.py)")
-    ap.add_argument("-c", "--config", default=None, help="resolved config JSON (e.g. rspnet_amd/config/finetune/c3d.json)")
-    ap.add_argument("-x", "--ext-config", action="append", help="JSON object merged over the config (may repeat)")
-    ap.add_argument("-e", "--experiment-dir", required=True)
-    ap.add_argument("--load-checkpoint", default=None, help="a fine-tune checkpoint: model, optimizer, scheduler, epoch")
+    ap = argparse.ArgumentParser(description="RSPNet action-recognition fine-tuning on MI355X (flag names follow the reference's arguments.py)")
+    add_driver_arguments(ap, "rspnet_amd/config/finetune/c3d.json", world_size=1)
     ap.add_argument("--moco-checkpoint", default=None, help="a pretext checkpoint: encoder_q.* feeds the backbone")
     ap.add_argument("--validate", action="store_true", help="only the final multi-crop validation of --load-checkpoint")
-    ap.add_argument("-d", "--debug", action="store_true", help="1 epoch, DEBUG logging")
-    ap.add_argument("--ws", "--world-size", dest="world_size", type=int, default=1)
-    ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--run-dir", default=None, help="default: EXP/run_{id}_{timestamp}")
-    ap.add_argument("--continue", dest="cont", action="store_true", help="use the previous run's config and EXP/checkpoint.pth.tar")
-    ap.add_argument("--steps-per-epoch", type=int, default=100, help="synthetic train loader length")
     ap.add_argument("--val-samples", type=int, default=100, help="synthetic validation set size")
-    args = ap.parse_args(argv)
-    resolve_continue(args)
-    if args.config is None:
-        ap.error("-c/--config is required (or --continue with a previous run)")
-    args.run_dir = str(resolve_run_dir(args))
-    return args
+    return parse_driver_args(ap, argv)
 
 
 def main(argv=None):
-    from .pretrain import _free_port
-    args = parse_args(argv)
-    if args.world_size <= 1:
-        return main_worker(0, args, "")
-    torch.multiprocessing.spawn(main_worker, args=(args, f"tcp://127.0.0.1:{_free_port()}"), nprocs=args.world_size)
+    return launch(main_worker, parse_args(argv))
 
 
 if __name__ == "__main__":

@@ -13,24 +13,20 @@ saves as run_*/config.json (rspnet_amd/config/pretrain/*.json ship the four ship
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import logging
 import math
 import os
-import re
-import socket
-import sys
 import time
-from datetime import datetime
 from pathlib import Path
-from shlex import quote
 
-import numpy as np
 import torch
-import torch.distributed as dist
 
 from . import _lib, ops
+from .framework.arguments import RUN_DIR_NAME_REGEX, add_driver_arguments, parse_driver_args, save_run_files  # noqa: F401
+from .framework.driver import (append_scalars, finish_process_group, init_process_group, launch, load_config, load_states, save_run,
+                               seed_everything, setup_logging, visible_gpu_count)
+from .framework.meters import DeviceMeters
 from .framework.utils.checkpoint import CheckpointManager
 from .framework.utils.environment import scale_learning_rate
 from .moco import Loss, ModelFactory
@@ -64,51 +60,14 @@ def pretext_accuracy(output, ranking_logits) -> torch.Tensor:
     return torch.stack(hits).to(torch.float32) * (100.0 / B)                      # classification.py:18-19
 
 
-class PretextMeters:
-    """The eight running meters of a pretext epoch (pretrain.py:97-106; framework/meters/average.py) as ONE device struct,
-    rsp_pretext_meters: val[8] / sum[8] fp32, count[8] int32.  rsp_pretext_metrics updates it on the device; ``read`` is the only
-    host synchronisation."""
+class PretextMeters(DeviceMeters):
+    """The eight running meters of a pretext epoch (pretrain.py:97-106) over rsp_pretext_meters; rsp_pretext_metrics updates them on
+    the device."""
 
     NAMES = ("Loss", "Loss_A", "Acc@1_A", "Acc@5_A", "Acc@1_A_n", "Acc@5_A_n", "Loss_M", "Acc@1_M")
     KEYS = ("loss", "loss_A", "acc1_A", "acc5_A", "acc1_A_n", "acc5_A_n", "loss_M", "acc1_M")
     FMTS = (":f", ":f", ":6.2f", ":6.2f", ":6.2f", ":6.2f", ":f", ":6.2f")
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        self.buf = torch.zeros(ctypes.sizeof(_lib.PretextMeters), dtype=torch.uint8, device=self.device)
-        self.val = self.buf[0:32].view(torch.float32)
-        self.sum = self.buf[32:64].view(torch.float32)
-        self.count = self.buf[64:96].view(torch.int32)
-
-    def reset(self):
-        self.buf.zero_()
-
-    @torch.no_grad()
-    def update(self, values, n: int):
-        """AverageMeter.update(v_i, n) for the eight values in KEYS order from torch ops -- the path of a backend without the HIP
-        entry point, and of host tensors."""
-        v = torch.stack([x.detach().to(torch.float32).reshape(()) for x in values]).to(self.device)
-        self.val.copy_(v)
-        self.sum += v * n
-        self.count += n
-
-    def read(self):
-        """{key: {val, avg, sum, count}}; avg = sum / count in fp32 (NaN while count is 0).  Synchronises."""
-        host = self.buf.cpu().numpy()
-        val, total, count = host[0:32].view(np.float32), host[32:64].view(np.float32), host[64:96].view(np.int32)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            avg = total / count.astype(np.float32)
-        return {k: {"val": float(val[i]), "avg": float(avg[i]), "sum": float(total[i]), "count": int(count[i])}
-                for i, k in enumerate(self.KEYS)}
-
-    def pieces(self, stats=None):
-        """['Loss {val:f} ({avg:f})', 'Loss_A ...', 'Acc@1_A {val:6.2f} ({avg:6.2f})', ...] as AverageMeter.__str__ formats them."""
-        stats = stats or self.read()
-        return [("{name} {val" + fmt + "} ({avg" + fmt + "})").format(name=name, val=stats[k]["val"], avg=stats[k]["avg"])
-                for name, k, fmt in zip(self.NAMES, self.KEYS, self.FMTS)]
-
-    def __str__(self):
-        return "\t".join(self.pieces())
+    STRUCT = _lib.PretextMeters
 
 
 def _losses3(loss, loss_A, loss_M) -> torch.Tensor:
@@ -216,14 +175,8 @@ class Engine:
                                                            seed=args.seed + local_rank)
 
     # ---- checkpoints (pretrain.py:112-132) ---------------------------------------------------------------------------
-    def _load_ckpt_file(self, path):
-        states = torch.load(path, map_location=self.device, weights_only=False)
-        if states["arch"] != self.arch:
-            raise ValueError(f'Loading checkpoint arch {states["arch"]} does not match current arch {self.arch}')
-        return states
-
     def load_checkpoint(self, path):
-        states = self._load_ckpt_file(path)
+        states = load_states(path, self.device, self.arch)
         self.model.module.load_state_dict(states["model"])
         self.optimizer.load_state_dict(states["optimizer"])
         self.scheduler.load_state_dict(states["scheduler"])
@@ -231,7 +184,7 @@ class Engine:
         self.best_loss = states["best_loss"]
 
     def load_model(self, path):
-        self.model.module.load_state_dict(self._load_ckpt_file(path)["model"])
+        self.model.module.load_state_dict(load_states(path, self.device, self.arch)["model"])
 
     # ---- training (pretrain.py:147-260) ------------------------------------------------------------------------------
     def _update_meters(self, loss, loss_A, loss_M, output, ranking_logits):
@@ -295,13 +248,9 @@ class Engine:
 
     def _write_scalars(self, lr: float):
         """One line per epoch in RUN_DIR/scalars.jsonl (rank 0): what pretrain.py:199-218,240 hands to the summary writer."""
-        if self.scalars_path is None:
-            return
         rec = {"epoch": self.current_epoch, "train/lr": lr}
         rec.update({f"train/{k}": self.stats[k]["avg"] for k in ("loss", "loss_A", "acc1_A", "acc5_A", "loss_M", "acc1_M")})
-        self.scalars_path.parent.mkdir(parents=True, exist_ok=True)
-        with open(self.scalars_path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
+        append_scalars(self.scalars_path, rec)
 
     def run(self):
         num_epochs = 1 if self.args.debug else self.num_epochs
@@ -332,194 +281,44 @@ class Engine:
         return stats
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-RUN_DIR_NAME_REGEX = re.compile(r"^run_(\d+)_")
-
-
-def resolve_run_dir(args) -> Path:
-    """EXP/run_{id}_{timestamp}: id = 1 + the highest existing run id (framework/arguments.py:64-78)."""
-    if args.run_dir is not None:
-        return Path(args.run_dir)
-    exp = Path(args.experiment_dir)
-    run_id = -1
-    if exp.exists():
-        for prev in exp.iterdir():
-            m = RUN_DIR_NAME_REGEX.match(prev.name)
-            if m is not None:
-                run_id = max(run_id, int(m.group(1)))
-    return exp / f"run_{run_id + 1}_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
-
-
-def resolve_continue(args):
-    """--continue: newest run's config.json and EXP/checkpoint.pth.tar (arguments.py:59-86)."""
-    if not args.cont:
-        return
-    exp = Path(args.experiment_dir)
-    if not exp.exists():
-        raise EnvironmentError(f'Experiment directory "{exp}" does not exists.')
-    if args.config is None:
-        best = -1
-        for run in exp.iterdir():
-            m = RUN_DIR_NAME_REGEX.match(run.name)
-            if m is not None and int(m.group(1)) > best and run.is_dir() and (run / "config.json").exists():
-                best = int(m.group(1))
-                args.config = str(run / "config.json")
-        if args.config is None:
-            raise EnvironmentError("No previous run config found")
-        logger.info('Continue using previous config: "%s"', args.config)
-    if args.load_checkpoint is None:
-        ckpt = exp / "checkpoint.pth.tar"
-        if ckpt.exists():
-            args.load_checkpoint = str(ckpt)
-            logger.info('Continue using previous checkpoint: "%s"', ckpt)
-        else:
-            logger.warning("No previous checkpoint found")
-
-
-def save_run_files(args, cfg: dict):
-    """run dir contents: config.json (framework/config.py:78-81), run.sh (framework/arguments.py:49-58), experiment.log."""
-    run_dir = Path(args.run_dir)
-    run_dir.mkdir(parents=True, exist_ok=True)
-    with open(run_dir / "config.json", "w") as f:
-        json.dump(cfg, f, indent=2)
-    with open(run_dir / "run.sh", "w") as f:
-        f.write(f"cd {quote(os.getcwd())}\n")
-        for env in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):
-            if os.environ.get(env) is not None:
-                f.write(f"export {env}={quote(os.environ[env])}\n")
-        f.write(sys.executable + " " + " ".join(quote(a) for a in sys.argv) + "\n")
-
-
 def main_worker(local_rank: int, args, dist_url: str):
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO, format="%(asctime)s %(message)s")
-    if local_rank == 0 and args.run_dir is not None:
-        Path(args.run_dir).mkdir(parents=True, exist_ok=True)
-        logging.getLogger().addHandler(logging.FileHandler(Path(args.run_dir) / "experiment.log"))   # framework/logging.py:31
-    import random
-    import numpy as np
-    seed = args.seed + local_rank                                   # utils/reproduction.py initialize_seed (pretrain.py:266-267)
-    random.seed(seed)
-    np.random.seed(seed)
-    torch.manual_seed(seed)
+    setup_logging(args, local_rank)
+    seed_everything(args.seed + local_rank)                         # utils/reproduction.py initialize_seed (pretrain.py:266-267)
     torch.cuda.set_device(local_rank)
     forced = args.world_size <= 1 and bool(os.environ.get("RSP_FORCE_COLLECTIVES"))      # one rank, RCCL path on (see MoCoDiffLossTwoFc)
-    if args.world_size > 1 or forced:
-        dist.init_process_group("nccl", init_method=dist_url or f"tcp://127.0.0.1:{_free_port()}", rank=local_rank,
-                                world_size=max(args.world_size, 1), device_id=torch.device("cuda", local_rank))
-    with open(args.config) as f:
-        cfg = json.load(f)
-    for snippet in args.ext_config or []:                           # -x overlays: JSON objects merged on top
-        _merge(cfg, json.loads(snippet))
+    group = init_process_group(args, local_rank, dist_url, forced)
+    cfg = load_config(args.config, args.ext_config)
     replace_moco_k_in_config(cfg)
-    if local_rank == 0:
-        Path(args.experiment_dir).mkdir(parents=True, exist_ok=True)
-        save_run_files(args, cfg)
+    save_run(args, cfg, local_rank)
     engine = Engine(args, cfg, local_rank)
     if args.load_model is not None:
         engine.load_model(args.load_model)
     if args.load_checkpoint is not None:
         engine.load_checkpoint(args.load_checkpoint)
     stats = engine.run()
-    if args.world_size > 1 or forced:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish_process_group(group)
     return stats
-
-
-def _merge(base: dict, over: dict):
-    for k, v in over.items():
-        if isinstance(v, dict) and isinstance(base.get(k), dict):
-            _merge(base[k], v)
-        else:
-            base[k] = v
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="RSPNet pretext training on MI355X (flag names follow the reference's arguments.py)")
-    ap.add_argument("-c", "--config", default=None, help="resolved config JSON (e.g. rspnet_amd/config/pretrain/c3d.json)")
-    ap.add_argument("-x", "--ext-config", action="append", help="JSON object merged over the config (may repeat)")
-    ap.add_argument("-e", "--experiment-dir", required=True)
-    ap.add_argument("--load-checkpoint", default=None)
+    add_driver_arguments(ap, "rspnet_amd/config/pretrain/c3d.json", world_size=None)
     ap.add_argument("--load-model", default=None)
-    ap.add_argument("-d", "--debug", action="store_true", help="1 epoch, DEBUG logging, allows --ws 1 (pretrain.py:312-316)")
-    ap.add_argument("--ws", "--world-size", dest="world_size", type=int, default=None)
-    ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-scale-lr", action="store_true")
-    ap.add_argument("--steps-per-epoch", type=int, default=100, help="synthetic loader length")
     ap.add_argument("--validate", action="store_true",
                     help="one epoch of forward, loss and meters without optimisation (pretrain.py:162)")
     ap.add_argument("--no-graph", action="store_true", help="never replay the step as captured HIP graphs (default: only when the host is the limiter)")
     ap.add_argument("--loader", choices=("tensor", "uint8"), default="tensor",
                     help="tensor: fixed N(0,1) device clips; uint8: synthetic uint8 videos -> CPU random crop -> fused GPU augmentation")
-    ap.add_argument("--run-dir", default=None, help="default: EXP/run_{id}_{timestamp}")
-    ap.add_argument("--continue", dest="cont", action="store_true", help="use the previous run's config and EXP/checkpoint.pth.tar")
-    args = ap.parse_args(argv)
-    resolve_continue(args)
-    if args.config is None:
-        ap.error("-c/--config is required (or --continue with a previous run)")
-    args.run_dir = str(resolve_run_dir(args))     # resolved once, before the workers are spawned
+    args = parse_driver_args(ap, argv)
     if args.world_size is None:
         args.world_size = visible_gpu_count()
     return args
 
 
-def visible_gpu_count() -> int:
-    """Number of GPUs this launcher spawns ranks for — what the reference asks torch.cuda.device_count() for (pretrain.py:318) —
-    found WITHOUT touching the HIP runtime in the parent: ranks are fresh child processes and the launcher itself must stay
-    GPU-free (a process that has initialised the GPU must never be re-exec'ed or forked on this platform).  A short-lived CHILD
-    interpreter is asked for torch.cuda.device_count(): it sees exactly what a rank will see (HIP_/ROCR_/CUDA_VISIBLE_DEVICES,
-    container device filtering).  Only if that child cannot be run, the count falls back to the KFD topology intersected with the
-    *_VISIBLE_DEVICES lists.  Raises when no GPU is visible."""
-    import subprocess
-    n = None
-    try:
-        r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True, text=True,
-                           timeout=300)
-        if r.returncode == 0:
-            n = int(r.stdout.strip().splitlines()[-1])
-    except (OSError, ValueError, IndexError, subprocess.TimeoutExpired):
-        n = None
-    if n is None:
-        n = _kfd_gpu_count()
-        for var in ("ROCR_VISIBLE_DEVICES", "HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):      # each list filters the previous one
-            v = os.environ.get(var)
-            if v is not None:
-                n = min(n, len([t for t in v.split(",") if t.strip() != ""]))
-    if n <= 0:
-        raise EnvironmentError("rspnet_amd.pretrain: no GPU is visible to this process (check HIP_VISIBLE_DEVICES / "
-                               "ROCR_VISIBLE_DEVICES and the container's /dev/kfd, /dev/dri access); pass --ws to override")
-    return n
-
-
-def _kfd_gpu_count() -> int:
-    """GPUs in the KFD topology (nodes with simd_count > 0)."""
-    import glob
-    n = 0
-    for path in glob.glob("/sys/class/kfd/kfd/topology/nodes/*/properties"):
-        try:
-            with open(path) as f:
-                props = dict(line.split()[:2] for line in f if len(line.split()) >= 2)
-            if int(props.get("simd_count", "0")) > 0:
-                n += 1
-        except (OSError, ValueError):
-            continue
-    return n
-
-
 def main(argv=None):
-    args = parse_args(argv)
     # Unlike the reference (which needs >= 2 ranks for shuffle-BN unless --debug), one GPU is a supported configuration.
-    if args.world_size <= 1:
-        return main_worker(0, args, "")
-    url = f"tcp://127.0.0.1:{_free_port()}"
-    torch.multiprocessing.spawn(main_worker, args=(args, url), nprocs=args.world_size)
+    return launch(main_worker, parse_args(argv))
 
 
 if __name__ == "__main__":

@@ -18,16 +18,15 @@ not half the channel count (``clip_q.shape[1] // 2`` = 1); key maps are paired w
 from __future__ import annotations
 
 import argparse
-import json
 import logging
 import os
-import random
 from typing import Iterable, Optional
 
 import numpy as np
 import torch
 
 from . import ops as _ops
+from .framework.driver import load_config, load_states, seed_everything
 from .moco import ModelFactory
 from .utils.moco import replace_moco_k_in_config
 
@@ -40,9 +39,9 @@ def visualization_loader(batch_size: int, T: int, size: int, steps: int, device,
     """The synthetic uint8 video source of pretrain.py behind the reference's visualisation chain
     (datasets/classification/__init__.py:183-188: ToTensor + Resize — no grayscale, jitter or flip, mean 0, std 1): un-normalised
     [0, 1] clips."""
+    from . import pretrain                       # the pretext driver owns the synthetic video source
     from .augment import FusedGPUCollateFn
-    from .pretrain import SyntheticVideoClips
-    loader = SyntheticVideoClips(batch_size, T, size, steps, device, seed=seed, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0))
+    loader = pretrain.SyntheticVideoClips(batch_size, T, size, steps, device, seed=seed, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0))
     loader.collate = FusedGPUCollateFn(size, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), p_gray=0.0, brightness=0, contrast=0, saturation=0,
                                        hue=0, p_flip=0.0, target_transform=False, device=device)
     return loader
@@ -64,9 +63,7 @@ class Engine:
 
     def load_model(self, checkpoint_path: str):
         """visualization.py:41-50: the architecture check, then a strict load_state_dict."""
-        states = torch.load(checkpoint_path, map_location=self.device, weights_only=False)
-        if states["arch"] != self.arch:
-            raise ValueError(f'Loading checkpoint arch {states["arch"]} does not match current arch {self.arch}')
+        states = load_states(checkpoint_path, self.device, self.arch)
         msg = self.model.module.load_state_dict(states["model"])
         logger.info("Missing keys: %s, Unexpected keys: %s", msg.missing_keys, msg.unexpected_keys)
         return msg
@@ -138,17 +135,10 @@ def parse_args(argv=None):
 
 def main(argv=None, loader: Optional[Iterable] = None, device=None):
     """Single process, rank 0.  ``loader`` / ``device``: for callers with their own clips (and the host-logic tests)."""
-    from .pretrain import _merge
     args = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
-    if args.seed is not None:                      # utils/reproduction.py initialize_seed (visualization.py:121-122)
-        random.seed(args.seed)
-        np.random.seed(args.seed)
-        torch.manual_seed(args.seed)
-    with open(args.config) as f:
-        cfg = json.load(f)
-    for snippet in args.ext_config or []:
-        _merge(cfg, json.loads(snippet))
+    seed_everything(args.seed)                     # utils/reproduction.py initialize_seed (visualization.py:121-122)
+    cfg = load_config(args.config, args.ext_config)
     replace_moco_k_in_config(cfg)
     os.makedirs(args.experiment_dir, exist_ok=True)
     if device is None:
