@@ -137,8 +137,11 @@ const char* rsp_conv3d_kernel_name(const rsp_conv3d_desc* d, int which);
 double rsp_conv3d_executed_fraction(const rsp_conv3d_desc* d, int which);
 
 /* Planning options of the convolution launchers, settable at run time (process-wide; host arithmetic only: which kernel instance and
- * which K split a descriptor gets — every choice computes the same convolution, in another summation order).  Returns the previous
- * value, or RSP_EINVAL for an unknown name.
+ * which K split a descriptor gets — every choice computes the same convolution, in another summation order).  One table (csrc/common.h
+ * RSP_CONV_OPTIONS) holds each option's name, environment variable and default.  An option's value is what was stored here (>= 0),
+ * else its environment variable (read once per process; an integer through atoi, a flag set when the variable is present at all),
+ * else the default; a value < 0 goes back to the environment / the default.  Returns the previous EFFECTIVE value, or RSP_EINVAL
+ * ("unknown option") for a name that is not in the table.
  *   "narrow_max_tiles"    launches of fewer than this many 128-wide tiles (and 97..128 or > 160 columns) run on the 64-wide tile
  *                         (default 512, environment RSP_NARROW_MAX_TILES; 0: never; < 0: back to the default).
  *   "narrow32_max_units"  launches of at most this many 128 x 64 tiles (more than 32 columns, K of at least 8 chunks) run on the
@@ -150,6 +153,15 @@ double rsp_conv3d_executed_fraction(const rsp_conv3d_desc* d, int which);
  *   "two_level_min_chunks" slice-major 128-wide launches of at least this many 32-deep K chunks sum K in panels of 512 products
  *                         (a second accumulator set, two waves per SIMD): the CPU convolution's error level on the long-K layers
  *                         (default 0 = never: priced in round 6; environment RSP_TWO_LEVEL_MIN_CHUNKS).
+ *   "direct_max_tiles"    launches of at most this many 128 x 128 tiles with Cin % 16 == 0 run on igemm_direct_kernel (default 0 =
+ *                         never: superseded by the 64-wide tiles; environment RSP_DIRECT_MAX_TILES).
+ * Flags (default 0; 1 switches the fast path off, for A/B measurements):
+ *   "no_persist"          RSP_NO_PERSIST       per-tile instead of persistent implicit-GEMM kernels
+ *   "no_half_block"       RSP_NO_HALF_BLOCK    the 160-wide / 32-row instances instead of those with a 16-wide MFMA block
+ *   "no_pad_skip"         RSP_NO_PAD_SKIP      no skipping of K chunks / row chunks that fall into the padding
+ *   "no_dmajor"           RSP_NO_DMAJOR        no depth-major row order
+ *   "no_tm_skip"          RSP_NO_TM_SKIP       no dead-tap skipping on the tap-major walk
+ *   "no_multi_split"      RSP_NO_MULTI_SPLIT   few-tile strided input gradients: no common K split of the classes that share a launch
  * Used by the kernel tests (an instance at sizes the checker finishes in seconds) and by tools/geom_bench.py (A/B of a plan in one
  * process).  The whole-step parity tests run under the DEFAULT plan only. */
 int rsp_conv3d_set_option(const char* name, int32_t value);

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <tuple>
 
 #include "rspnet_hip.h"
 
@@ -21,11 +22,47 @@ static inline int rsp_check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+    snprintf(buf, sizeof buf, "%.*s: %s", (int)strcspn(what, "<"), what, hipGetErrorString(e));      // (a name, or a note format: up to its '<')
     rsp_set_error(buf);
     return RSP_ELAUNCH;
   }
   return RSP_OK;
+}
+
+// Planning options of the convolution launchers: the one table behind rsp_conv3d_set_option (conv_options.hip).  Columns: enum
+// constant, option name, environment variable, flag (1: the variable counts as set when present, whatever its value) or integer
+// (0: atoi), built-in default.  The planning functions look an option up by its constant: one relaxed atomic load + the cached
+// environment value, no string comparison on the launch path.
+#define RSP_CONV_OPTIONS(X)                                                             \
+  X(OPT_NARROW_MAX_TILES, "narrow_max_tiles", "RSP_NARROW_MAX_TILES", 0, 512)           \
+  X(OPT_NARROW32_MAX_UNITS, "narrow32_max_units", "RSP_NARROW32_MAX_UNITS", 0, 256)     \
+  X(OPT_TALL_MIN_TILES, "tall_min_tiles", "RSP_TALL_MIN_TILES", 0, 0)                   \
+  X(OPT_TWO_LEVEL_MIN_CHUNKS, "two_level_min_chunks", "RSP_TWO_LEVEL_MIN_CHUNKS", 0, 0) \
+  X(OPT_DIRECT_MAX_TILES, "direct_max_tiles", "RSP_DIRECT_MAX_TILES", 0, 0)             \
+  X(OPT_NO_PERSIST, "no_persist", "RSP_NO_PERSIST", 1, 0)                               \
+  X(OPT_NO_HALF_BLOCK, "no_half_block", "RSP_NO_HALF_BLOCK", 1, 0)                      \
+  X(OPT_NO_PAD_SKIP, "no_pad_skip", "RSP_NO_PAD_SKIP", 1, 0)                            \
+  X(OPT_NO_DMAJOR, "no_dmajor", "RSP_NO_DMAJOR", 1, 0)                                  \
+  X(OPT_NO_TM_SKIP, "no_tm_skip", "RSP_NO_TM_SKIP", 1, 0)                               \
+  X(OPT_NO_MULTI_SPLIT, "no_multi_split", "RSP_NO_MULTI_SPLIT", 1, 0)
+#define RSP_OPTION_ID(id, name, env, flag, dflt) id,
+enum RspConvOption { RSP_CONV_OPTIONS(RSP_OPTION_ID) RSP_OPT_COUNT };
+#undef RSP_OPTION_ID
+int rsp_conv_option(RspConvOption id);      // the effective value: set_option's if >= 0, else the environment's, else the default
+
+// Launch (256 threads) of a kernel instance whose dynamic LDS can exceed the default limit.  KERNEL is a template argument, so
+// the "attribute raised" flag is the instance's own: hipFuncAttributeMaxDynamicSharedMemorySize goes to lds_max on its first launch.
+// `args`: the kernel's arguments (std::tie); `fmt, note...`: how the instance is spelled (rsp_note_kernel).
+template <auto KERNEL, class... Args, class... Note>
+int rsp_launch_lds(dim3 grid, size_t lds, size_t lds_max, hipStream_t s, const std::tuple<Args...>& args, const char* fmt, Note... note) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+    attr_set = true;
+  }
+  rsp_note_kernel(fmt, note...);
+  std::apply([&](const auto&... a) { hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds, s, a...); }, args);
+  return rsp_check_launch(fmt);
 }
 
 #define RSP_REQUIRE(cond, msg)     \

@@ -16,7 +16,6 @@
 // input are served by L2 (27 x re-read of conv2's 411 MB input = 1.6 TB/s of L2 traffic, L2 peak 34 TB/s).
 #include "common.h"
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 #include "conv_stem.h"
 
@@ -1900,41 +1899,27 @@ constexpr const char* kernel_format(KernelFamily f) {      // arguments: BM, BN,
                              : "igemm_multi_kernel<%d, %d, %d, %d, %d, %d>";
 }
 
+// Dynamic LDS of the per-tile kernels (igemm_kernel, igemm_ks_kernel, igemm_multi_kernel): the tile buffers (kw floats per row:
+// BK on the LDS-DMA path, LDK on the scalar-gather one) + tap table (sized by the actual tap count: short-K layers are latency-bound
+// and want a third workgroup per CU) + output-row address table.  The attribute's maximum is tile_lds(.., 2, MAX_TAPS).
+constexpr size_t tile_lds(int bm, int bn, int kw, int nbuf, int taps) {
+  return (size_t)nbuf * (bm + bn) * kw * sizeof(float) + (size_t)(taps + 1) * sizeof(int4) + bm * sizeof(long long);
+}
+inline dim3 tile_grid(const IgemmParams& p) { return dim3(p.full_tiles + (p.m_tiles * p.n_tiles - p.full_tiles) * p.splitk); }
+
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 int launch_ks_cfg(const IgemmParams& p, hipStream_t s) {
-  const size_t lds = (size_t)p.nbuf * (BM + BN) * BK * sizeof(float) + (size_t)(p.nTd * p.nTh * p.nTw + 1) * sizeof(int4) + BM * sizeof(long long);
-  static bool attr_set = false;
-  if (!attr_set) {
-    const size_t lds_max = (size_t)2 * (BM + BN) * BK * sizeof(float) + (MAX_TAPS + 1) * sizeof(int4) + BM * sizeof(long long);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_ks_kernel<BM, BN, WAVES_M, WAVES_N>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-    attr_set = true;
-  }
-  dim3 grid(p.full_tiles + (p.m_tiles * p.n_tiles - p.full_tiles) * p.splitk);
-  rsp_note_kernel(kernel_format(K_TILE_KS), BM, BN, WAVES_M, WAVES_N);
-  hipLaunchKernelGGL((igemm_ks_kernel<BM, BN, WAVES_M, WAVES_N>), grid, dim3(256), lds, s, p);
-  return rsp_check_launch("igemm_ks_kernel");
+  return rsp_launch_lds<&igemm_ks_kernel<BM, BN, WAVES_M, WAVES_N>>(
+      tile_grid(p), tile_lds(BM, BN, BK, p.nbuf, p.nTd * p.nTh * p.nTw), tile_lds(BM, BN, BK, 2, MAX_TAPS), s, std::tie(p),
+      kernel_format(K_TILE_KS), BM, BN, WAVES_M, WAVES_N);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int VEC, int MINW = 2>
 int launch_cfg(const IgemmParams& p, hipStream_t s) {
-  // LDS: two tile buffers + tap table (sized by the actual tap count: short-K layers are latency-bound and want a
-  // third workgroup per CU) + output-row address table
-  const size_t nb = VEC == 4 ? (size_t)p.nbuf : 2;
-  const size_t lds = nb * (BM + BN) * (VEC == 4 ? BK : LDK) * sizeof(float) +
-                     (size_t)(p.nTd * p.nTh * p.nTw + 1) * sizeof(int4) + BM * sizeof(long long);
-  static bool attr_set = false;
-  if (!attr_set) {
-    const size_t lds_max = (size_t)2 * (BM + BN) * (VEC == 4 ? BK : LDK) * sizeof(float) + (MAX_TAPS + 1) * sizeof(int4) +
-                           BM * sizeof(long long);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<BM, BN, WAVES_M, WAVES_N, VEC, MINW>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-    attr_set = true;
-  }
-  dim3 grid(p.full_tiles + (p.m_tiles * p.n_tiles - p.full_tiles) * p.splitk);
-  rsp_note_kernel(kernel_format(K_TILE), BM, BN, WAVES_M, WAVES_N, VEC, MINW);
-  hipLaunchKernelGGL((igemm_kernel<BM, BN, WAVES_M, WAVES_N, VEC, MINW>), grid, dim3(256), lds, s, p);
-  return rsp_check_launch("igemm_kernel");
+  constexpr int KW = VEC == 4 ? BK : LDK;
+  return rsp_launch_lds<&igemm_kernel<BM, BN, WAVES_M, WAVES_N, VEC, MINW>>(
+      tile_grid(p), tile_lds(BM, BN, KW, VEC == 4 ? p.nbuf : 2, p.nTd * p.nTh * p.nTw), tile_lds(BM, BN, KW, 2, MAX_TAPS), s, std::tie(p),
+      kernel_format(K_TILE), BM, BN, WAVES_M, WAVES_N, VEC, MINW);
 }
 
 // N-tile width of a column segment.  Besides 128 / 64 / 32 there are two odd widths, run by 4 waves stacked along M (each wave
@@ -1953,34 +1938,24 @@ inline int tile_bn(int Cout) {
 // 7 x 7 / 4 x 4 layers +1-3 %; per step S3D-G 405.3 -> 412.5 (+1.8 %) and +0.25 % more with the 97..128-column launches included,
 // R3D-18 +0.8 %, R(2+1)D +0.1 %, C3D -0.1 % (conv5: noise).  Launches of a full round or more lose up to 1 % (the 64-wide tile re-reads the
 // A operand for half as many MFMAs: C3D -0.8 % with the limit at 1024 tiles) and keep the wide tile.
-std::atomic<int> g_narrow_max_tiles{-1};      // >= 0: set through rsp_conv3d_set_option; -1: the environment / the default
-static int narrow_max_tiles() {
-  const int set = g_narrow_max_tiles.load(std::memory_order_relaxed);
-  if (set >= 0) return set;
-  static const int v = getenv("RSP_NARROW_MAX_TILES") ? atoi(getenv("RSP_NARROW_MAX_TILES")) : 512;      // (0: off; A/B switch, read once)
-  return v;
-}
+// Option "narrow_max_tiles" (default 512; 0: off).
+//
 // Launches of less than one UNIT per CU even on the 64-wide tile (round 6): S3D-G's 14 x 14 / 7 x 7 pointwise and (3,1,1) layers, R3D-18's
 // layer3 / layer4 — 98 ... 256 tiles of 128 x 64.  Until round 5 they were cut along K (plan_split) to give every CU work, at the price
 // of a partial round trip and a dependent reduce launch per convolution (121 per S3D-G step, 73 per R3D-18 step: +4.8 % / +4.2 % per step
 // if they vanished, profiles/r05/experiments_r5.txt).  On the 32-wide tile the same launch has twice the units with the WHOLE K each:
 // no partials, no second pass, one summation order per output.  (The 32-wide tile reads the A operand for a quarter of the 128-wide
 // tile's MFMAs — irrelevant here: a launch this small is bound by the latency of its few chunks, not by L2 bandwidth.)
-std::atomic<int> g_narrow32_max_units{-1};
-static int narrow32_max_units() {
-  const int set = g_narrow32_max_units.load(std::memory_order_relaxed);
-  if (set >= 0) return set;
-  static const int v = getenv("RSP_NARROW32_MAX_UNITS") ? atoi(getenv("RSP_NARROW32_MAX_UNITS")) : 256;      // (0: off; A/B switch, read once)
-  return v;
-}
-// 0: the column count's own tile (tile_bn); 64 / 32: that tile width over all columns (no column segments)
+// Option "narrow32_max_units" (default 256; 0: off).
+//
+// narrow_bn returns 0: the column count's own tile (tile_bn); 64 / 32: that tile width over all columns (no column segments)
 inline int narrow_bn(long long M, int Cout, int nchunks) {
   const long long mt = rsp_cdiv(M, 128);
-  if (Cout > 32 && nchunks >= 8 && mt * rsp_cdiv(Cout, 64) <= narrow32_max_units()) return 32;
+  if (Cout > 32 && nchunks >= 8 && mt * rsp_cdiv(Cout, 64) <= rsp_conv_option(OPT_NARROW32_MAX_UNITS)) return 32;
   // (97..128 and > 160 columns: whole 64-wide tiles or nearly; 65..96 / 129..160 keep their 96- / 160-wide tile, whose last 64-wide
   //  tile would be half empty)
   const bool cols = Cout > 160 || (Cout > 96 && Cout <= 128);
-  return (cols && mt * rsp_cdiv(Cout, 128) < narrow_max_tiles()) ? 64 : 0;
+  return (cols && mt * rsp_cdiv(Cout, 128) < rsp_conv_option(OPT_NARROW_MAX_TILES)) ? 64 : 0;
 }
 
 // 256 x 64 tiles for 33..64-column launches (round 6): four waves stacked along M, each 64 rows x 64 columns — the
@@ -1993,112 +1968,64 @@ inline int narrow_bn(long long M, int Cout, int nchunks) {
 // 1325.7 -> 1320.4 clips/s, R(2+1)D 445.2 -> 442.0, S3D-G 418.5 -> 412.7, C3D 355.2 -> 354.1 (its 64-column input gradient of conv2:
 // 136.6 -> 135.1 TF).  The 128 x 64 tile is not LDS-bound: what it loses against the 128 x 128 tile is the per-tile fixed cost, and a tile
 // twice as tall pays the same cost per MFMA.  "tall_min_tiles" > 0 selects the instance (kernel tests, re-measurements).
-std::atomic<int> g_tall_min_tiles{-1};
-static int tall_min_tiles() {
-  const int set = g_tall_min_tiles.load(std::memory_order_relaxed);
-  if (set >= 0) return set;
-  static const int v = getenv("RSP_TALL_MIN_TILES") ? atoi(getenv("RSP_TALL_MIN_TILES")) : 0;      // (0: off, the default; A/B switch, read once)
-  return v;
-}
 inline bool tall_tiles(long long M, int bn, bool vec4) {
-  const int lim = tall_min_tiles();
+  const int lim = rsp_conv_option(OPT_TALL_MIN_TILES);      // (0: off, the default)
   return vec4 && bn == 64 && lim > 0 && M / 256 >= lim;
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int VEC, int MINW = 2>
 int launch_multi_cfg(const IgemmMulti& m, int max_taps, hipStream_t s) {
-  const size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(float) + (size_t)(max_taps + 1) * sizeof(int4) + BM * sizeof(long long);
-  static bool attr_set = false;
-  if (!attr_set) {
-    const size_t lds_max = (size_t)2 * (BM + BN) * BK * sizeof(float) + (MAX_TAPS + 1) * sizeof(int4) + BM * sizeof(long long);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_multi_kernel<BM, BN, WAVES_M, WAVES_N, VEC, MINW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-    attr_set = true;
-  }
-  rsp_note_kernel(kernel_format(K_MULTI), BM, BN, WAVES_M, WAVES_N, VEC, MINW);
-  hipLaunchKernelGGL((igemm_multi_kernel<BM, BN, WAVES_M, WAVES_N, VEC, MINW>), dim3(m.start[m.n]), dim3(256), lds, s, m);
-  return rsp_check_launch("igemm_multi_kernel");
+  return rsp_launch_lds<&igemm_multi_kernel<BM, BN, WAVES_M, WAVES_N, VEC, MINW>>(
+      dim3(m.start[m.n]), tile_lds(BM, BN, BK, 2, max_taps), tile_lds(BM, BN, BK, 2, MAX_TAPS), s, std::tie(m), kernel_format(K_MULTI), BM,
+      BN, WAVES_M, WAVES_N, VEC, MINW);
 }
-
 
 // waves per SIMD the persistent instances are compiled for (launch bound) = workgroups per CU the grid is sized with
 constexpr int persist_minw(int bn, int bm = 128) { return bm > 128 ? 3 : (bn > 128 ? 2 : (bn > 64 ? 3 : 4)); }
 
-static bool persist_enabled() {
-  static const bool off = getenv("RSP_NO_PERSIST") != nullptr;      // (A/B switch for measurements, read once)
-  return !off;
+static bool persist_enabled() { return !rsp_conv_option(OPT_NO_PERSIST); }      // (A/B switch for measurements)
+
+// Dynamic LDS of the persistent kernels (bnl: the B tile's rows in LDS) and their grid: the resident workgroups, LDS- and
+// register-limited (max_wpc per CU); every workgroup walks units wg, wg + G, wg + 2G, ... (G a multiple of 8 when it is smaller
+// than the unit count, so that a workgroup's units keep its XCD's contiguous share of the tiles: rsp_xcd_remap)
+constexpr size_t persist_lds(int bm, int bnl, int waves_m, int nbuf, int taps) {
+  return (size_t)nbuf * (bm + bnl) * BK * sizeof(float) + (size_t)(taps + 2) / 2 * sizeof(int4) + bm * sizeof(unsigned) +
+         (size_t)waves_m * bnl * 2 * sizeof(float) + 4 * sizeof(unsigned) + sizeof(IgemmParams);
+}
+inline int persist_grid(int n_units, size_t lds, int max_wpc) {
+  int wpc = (int)(160 * 1024 / lds);
+  wpc = wpc > max_wpc ? max_wpc : (wpc < 1 ? 1 : wpc);
+  return n_units <= 256 * wpc ? n_units : 256 * wpc;
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool KS>
 int launch_persist_cfg(const IgemmParams& p, hipStream_t s) {
   constexpr int MINW = persist_minw(BN, BM);
-  const int ntaps = p.nTd * p.nTh * p.nTw;
   constexpr int BNL = (BN + 31) / 32 * 32;      // (B tile rows in LDS: whole 32-row groups, igemm_persist)
-  auto lds_of = [&](int nbuf, int taps) {
-    return (size_t)nbuf * (BM + BNL) * BK * sizeof(float) + (size_t)(taps + 2) / 2 * sizeof(int4) + BM * sizeof(unsigned) +
-           (size_t)WAVES_M * BNL * 2 * sizeof(float) + 4 * sizeof(unsigned) + sizeof(IgemmParams);
-  };
-  const size_t lds = lds_of(p.nbuf, ntaps);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_persist_kernel<BM, BN, WAVES_M, WAVES_N, KS, MINW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(2, MAX_TAPS));
-    attr_set = true;
-  }
-  const int n_units = p.full_tiles + (p.m_tiles * p.n_tiles - p.full_tiles) * p.splitk;
-  // resident workgroups: LDS- and register-limited; every workgroup walks units wg, wg + G, wg + 2G, ... (G a multiple of 8 when
-  // it is smaller than the unit count, so that a workgroup's units keep its XCD's contiguous share of the tiles: rsp_xcd_remap)
-  int wpc = (int)(160 * 1024 / lds);
-  wpc = wpc > MINW ? MINW : (wpc < 1 ? 1 : wpc);
-  int G = 256 * wpc;
-  if (n_units <= G) G = n_units;
-  rsp_note_kernel(kernel_format(K_PERSIST), BM, BN, WAVES_M, WAVES_N, KS ? "true" : "false", MINW);
-  hipLaunchKernelGGL((igemm_persist_kernel<BM, BN, WAVES_M, WAVES_N, KS, MINW>), dim3(G), dim3(256), lds, s, p, n_units);
-  return rsp_check_launch("igemm_persist_kernel");
+  const size_t lds = persist_lds(BM, BNL, WAVES_M, p.nbuf, p.nTd * p.nTh * p.nTw);
+  const int n_units = (int)tile_grid(p).x;
+  return rsp_launch_lds<&igemm_persist_kernel<BM, BN, WAVES_M, WAVES_N, KS, MINW>>(
+      dim3(persist_grid(n_units, lds, MINW)), lds, persist_lds(BM, BNL, WAVES_M, 2, MAX_TAPS), s, std::tie(p, n_units),
+      kernel_format(K_PERSIST), BM, BN, WAVES_M, WAVES_N, KS ? "true" : "false", MINW);
 }
 
 // Two-level summation over K on the long-K slice-major 128 x 128 launches (igemm_persist, FOLD): OFF by default — measured in round 6
 // (profiles/r06/experiments_r6.txt), see DESIGN.md section 2.  "two_level_min_chunks" (rsp_conv3d_set_option / RSP_TWO_LEVEL_MIN_CHUNKS):
 // launches of at least that many K chunks take the instance; 0: never.
 constexpr int FOLD_CHUNKS = 16;      // 512 products per panel
-std::atomic<int> g_two_level_min_chunks{-1};
-static int two_level_min_chunks() {
-  const int set = g_two_level_min_chunks.load(std::memory_order_relaxed);
-  if (set >= 0) return set;
-  static const int v = getenv("RSP_TWO_LEVEL_MIN_CHUNKS") ? atoi(getenv("RSP_TWO_LEVEL_MIN_CHUNKS")) : 0;
-  return v;
-}
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool KS, int FOLD>
 int launch_persist_fold_cfg(const IgemmParams& p, hipStream_t s) {
-  const int ntaps = p.nTd * p.nTh * p.nTw;
-  auto lds_of = [&](int nbuf, int taps) {
-    return (size_t)nbuf * (BM + BN) * BK * sizeof(float) + (size_t)(taps + 2) / 2 * sizeof(int4) + BM * sizeof(unsigned) +
-           (size_t)WAVES_M * BN * 2 * sizeof(float) + 4 * sizeof(unsigned) + sizeof(IgemmParams);
-  };
-  const size_t lds = lds_of(p.nbuf, ntaps);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_persist_fold_kernel<BM, BN, WAVES_M, WAVES_N, KS, FOLD>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(2, MAX_TAPS));
-    attr_set = true;
-  }
-  const int n_units = p.full_tiles + (p.m_tiles * p.n_tiles - p.full_tiles) * p.splitk;
-  int wpc = (int)(160 * 1024 / lds);
-  wpc = wpc > 2 ? 2 : (wpc < 1 ? 1 : wpc);
-  int G = 256 * wpc;
-  if (n_units <= G) G = n_units;
-  rsp_note_kernel(kernel_format(K_PERSIST_FOLD), BM, BN, WAVES_M, WAVES_N, KS ? "true" : "false", FOLD);
-  hipLaunchKernelGGL((igemm_persist_fold_kernel<BM, BN, WAVES_M, WAVES_N, KS, FOLD>), dim3(G), dim3(256), lds, s, p, n_units);
-  return rsp_check_launch("igemm_persist_fold_kernel");
+  const size_t lds = persist_lds(BM, BN, WAVES_M, p.nbuf, p.nTd * p.nTh * p.nTw);
+  const int n_units = (int)tile_grid(p).x;
+  return rsp_launch_lds<&igemm_persist_fold_kernel<BM, BN, WAVES_M, WAVES_N, KS, FOLD>>(
+      dim3(persist_grid(n_units, lds, 2)), lds, persist_lds(BM, BN, WAVES_M, 2, MAX_TAPS), s, std::tie(p, n_units),
+      kernel_format(K_PERSIST_FOLD), BM, BN, WAVES_M, WAVES_N, KS ? "true" : "false", FOLD);
 }
 
 // Segments of 129..144 columns: the 160-wide tile's plan (one N tile, same splits) on the instance whose fifth column block is 16
-// wide (igemm_persist, HALF).  RSP_NO_HALF_BLOCK=1: the 160-wide instance (A/B switch, read once).
-static bool half_block_cols(int cols) {
-  static const bool off = getenv("RSP_NO_HALF_BLOCK") != nullptr;
-  return !off && cols > 128 && cols <= 144;
-}
+// wide (igemm_persist, HALF).  "no_half_block" (RSP_NO_HALF_BLOCK): the 160-wide instance (A/B switch).
+static bool half_block_cols(int cols) { return !rsp_conv_option(OPT_NO_HALF_BLOCK) && cols > 128 && cols <= 144; }
 
 // ---- the launch plan: decided ONCE per convolution (plan_conv), then executed (run_igemm), named (rsp_conv3d_kernel_name), sized
 // (rsp_conv3d_*_workspace) and priced (rsp_conv3d_executed_fraction) from the same struct ---------------------------------------
@@ -2187,8 +2114,7 @@ inline void fill_fastdiv(IgemmParams& p) {
   p.adv_tap = BK / p.Cin;
   p.adv_ci = BK % p.Cin;
   p.kmajor = k_slice_major(p.Cin, p.nTd * p.nTh * p.nTw) ? 1 : 0;
-  static const bool no_skip = getenv("RSP_NO_PAD_SKIP") != nullptr;      // (A/B switches for measurements, read once)
-  static const bool no_dmajor = getenv("RSP_NO_DMAJOR") != nullptr;
+  const bool no_skip = rsp_conv_option(OPT_NO_PAD_SKIP), no_dmajor = rsp_conv_option(OPT_NO_DMAJOR);      // (A/B switches for measurements)
   p.skip_pad = no_skip ? 0 : 1;
   // parts: eight (one per XCD) when each part's frame still spans several tiles, else one
   p.Np = (p.Nb % 8 == 0 && (long long)(p.Nb / 8) * p.Gh * p.Gw >= 4 * 128) ? p.Nb / 8 : (p.Nb > 0 ? p.Nb : 1);
@@ -2199,7 +2125,7 @@ inline void fill_fastdiv(IgemmParams& p) {
   const int dhi = (p.Gd - 1) * p.sD + (p.offstep > 0 ? p.off0d + p.nTd - 1 : p.off0d);
   const int ntaps = p.nTd * p.nTh * p.nTw;
   p.cpt = p.Cin % BK == 0 ? p.Cin / BK : 0;
-  static const bool no_tm = getenv("RSP_NO_TM_SKIP") != nullptr;
+  const bool no_tm = rsp_conv_option(OPT_NO_TM_SKIP);
   // (padding in any dimension can make a tap dead for a whole tile, but only depth does so often enough to pay for the walk)
   p.dThw = fastdiv_make(p.nTh * p.nTw);
   p.tm_skip = (p.skip_pad && !no_tm && !p.kmajor && p.nTd > 1 && (dlo < 0 || dhi >= p.Di)) ? 1 : 0;
@@ -2332,14 +2258,11 @@ Segments plan_segments(int Cout) {
 // per SIMD); against 64-wide tiles it loses those too (eleven small geometries back to back: 361 vs 326 us, tools/geom_bench.py small).
 // RSP_DIRECT_MAX_TILES=N selects it for launches of at most N 128 x 128 tiles with Cin % 16 == 0 (re-measurements, and the GPU tests run
 // the small convolution cases through it in a child interpreter).
-static int direct_max_tiles() {
-  static const int v = getenv("RSP_DIRECT_MAX_TILES") ? atoi(getenv("RSP_DIRECT_MAX_TILES")) : 0;
-  return v;
-}
 bool direct_applies(long long M, int Cout, int Cin, int K, bool vec4) {
   (void)K;
-  if (!vec4 || direct_max_tiles() <= 0 || Cin % 16 != 0 || M <= 0) return false;
-  return (long long)rsp_cdiv(M, 128) * rsp_cdiv(Cout, 128) <= direct_max_tiles();
+  const int max_tiles = rsp_conv_option(OPT_DIRECT_MAX_TILES);
+  if (!vec4 || max_tiles <= 0 || Cin % 16 != 0 || M <= 0) return false;
+  return (long long)rsp_cdiv(M, 128) * rsp_cdiv(Cout, 128) <= max_tiles;
 }
 // K split of a direct launch: enough units for ~3 workgroups per CU, at least 4 chunks per slice
 struct DirectPlan {
@@ -2386,10 +2309,7 @@ static MultiSplit plan_multi_split(int n, const long long* M, const int* tiles, 
   }
   return ms;
 }
-static bool multi_split_enabled() {
-  static const bool off = getenv("RSP_NO_MULTI_SPLIT") != nullptr;      // (A/B switch for measurements, read once)
-  return !off;
-}
+static bool multi_split_enabled() { return !rsp_conv_option(OPT_NO_MULTI_SPLIT); }      // (A/B switch for measurements)
 // byte offset of the last output row from the output base pointer; + a segment's columns: the bytes reachable from it
 static unsigned long long out_span_bytes(const IgemmParams& p) {
   return ((unsigned long long)p.Nb * p.oDm * p.oHm * p.oWm - 1) * (unsigned long long)p.out_ld * 4ull;
@@ -2432,7 +2352,8 @@ LaunchPlan plan_segment(long long M, int c0, int cols, int nb, int nchunks, bool
   l.waves_m = square ? 2 : 4;
   l.waves_n = square ? 2 : 1;
   if (persist) {
-    const bool fold = kmajor && bm == 128 && bn == 128 && two_level_min_chunks() > 0 && nchunks >= two_level_min_chunks();
+    const int fold_min = rsp_conv_option(OPT_TWO_LEVEL_MIN_CHUNKS);
+    const bool fold = kmajor && bm == 128 && bn == 128 && fold_min > 0 && nchunks >= fold_min;
     l.family = fold ? K_PERSIST_FOLD : K_PERSIST;
     l.ks = kmajor;
     if (bn == 160 && half_block_cols(cols)) bn = 144;
@@ -3154,31 +3075,6 @@ int32_t rsp_conv3d_pack_jobs(const rsp_conv3d_desc* d, int32_t which, int32_t Co
 }
 
 void rsp_conv3d_pack_forget(const void* w_packed) { rsp_stem_forget_packed(w_packed); }
-
-int rsp_conv3d_set_option(const char* name, int32_t value) {
-  if (name && !strcmp(name, "narrow_max_tiles")) {
-    const int prev = narrow_max_tiles();
-    g_narrow_max_tiles.store(value < 0 ? -1 : value, std::memory_order_relaxed);
-    return prev;
-  }
-  if (name && !strcmp(name, "narrow32_max_units")) {
-    const int prev = narrow32_max_units();
-    g_narrow32_max_units.store(value < 0 ? -1 : value, std::memory_order_relaxed);
-    return prev;
-  }
-  if (name && !strcmp(name, "two_level_min_chunks")) {
-    const int prev = two_level_min_chunks();
-    g_two_level_min_chunks.store(value < 0 ? -1 : value, std::memory_order_relaxed);
-    return prev;
-  }
-  if (name && !strcmp(name, "tall_min_tiles")) {
-    const int prev = tall_min_tiles();
-    g_tall_min_tiles.store(value < 0 ? -1 : value, std::memory_order_relaxed);
-    return prev;
-  }
-  rsp_set_error("rsp_conv3d_set_option: unknown option");
-  return RSP_EINVAL;
-}
 
 int rsp_pack_run(const rsp_pack_job* jobs_device, int32_t n_jobs, int32_t max_blocks, void* stream) {
   RSP_REQUIRE(jobs_device && n_jobs > 0 && n_jobs <= 65535 && max_blocks > 0, "rsp_pack_run: bad argument");

@@ -649,49 +649,32 @@ __global__ void colsum_stage2(const float* __restrict__ part, int nblk, int C, f
   out[c] = (float)s;
 }
 
+// Dynamic LDS of the weight-gradient kernels: two buffers of both operand tiles; the LDS-DMA kernels add three row-geometry chunks.
+constexpr size_t wgrad_lds(int bm, int bn, bool dma) { return (size_t)2 * RK * (bm + bn) * sizeof(float) + (dma ? 3 * RK * sizeof(uint2) : 0); }
+inline dim3 wgrad_grid(const WgradParams& p) { return dim3((unsigned)(p.co_tiles * p.k_tiles) * (unsigned)p.splitm); }
+
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool VECA, bool VECB>
 int launch_w(const WgradParams& p, hipStream_t s) {
-  const size_t lds = (size_t)2 * RK * (BM + BN) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<BM, BN, WAVES_M, WAVES_N, VECA, VECB>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  dim3 grid((unsigned)(p.co_tiles * p.k_tiles) * (unsigned)p.splitm);
-  rsp_note_kernel("wgrad_kernel<%d, %d, %d, %d, *>", BM, BN, WAVES_M, WAVES_N);
-  hipLaunchKernelGGL((wgrad_kernel<BM, BN, WAVES_M, WAVES_N, VECA, VECB>), grid, dim3(256), lds, s, p);
-  return rsp_check_launch("wgrad_kernel");
+  constexpr size_t lds = wgrad_lds(BM, BN, false);
+  return rsp_launch_lds<&wgrad_kernel<BM, BN, WAVES_M, WAVES_N, VECA, VECB>>(wgrad_grid(p), lds, lds, s, std::tie(p),
+                                                                             "wgrad_kernel<%d, %d, %d, %d, *>", BM, BN, WAVES_M, WAVES_N);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 int launch_w_dma(const WgradParams& p, hipStream_t s) {
-  const size_t lds = (size_t)2 * RK * (BM + BN) * sizeof(float) + 3 * RK * sizeof(uint2);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_dma_kernel<BM, BN, WAVES_M, WAVES_N>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  dim3 grid((unsigned)(p.co_tiles * p.k_tiles) * (unsigned)p.splitm);
-  rsp_note_kernel("wgrad_dma_kernel<%d, %d, %d, %d>", BM, BN, WAVES_M, WAVES_N);
-  hipLaunchKernelGGL((wgrad_dma_kernel<BM, BN, WAVES_M, WAVES_N>), grid, dim3(256), lds, s, p);
-  return rsp_check_launch("wgrad_dma_kernel");
+  constexpr size_t lds = wgrad_lds(BM, BN, true);
+  return rsp_launch_lds<&wgrad_dma_kernel<BM, BN, WAVES_M, WAVES_N>>(wgrad_grid(p), lds, lds, s, std::tie(p),
+                                                                     "wgrad_dma_kernel<%d, %d, %d, %d>", BM, BN, WAVES_M, WAVES_N);
 }
 
-int launch_w_dma_h16(const WgradParams& p, hipStream_t s) {
-  const size_t lds = (size_t)2 * RK * (32 + 128) * sizeof(float) + 3 * RK * sizeof(uint2);
-  dim3 grid((unsigned)(p.co_tiles * p.k_tiles) * (unsigned)p.splitm);
+int launch_w_dma_h16(const WgradParams& p, hipStream_t s) {      // (41 KB: below the default limit, no attribute to raise)
   rsp_note_kernel("wgrad_dma_h16_kernel");
-  hipLaunchKernelGGL(wgrad_dma_h16_kernel, grid, dim3(256), lds, s, p);
+  hipLaunchKernelGGL(wgrad_dma_h16_kernel, wgrad_grid(p), dim3(256), wgrad_lds(32, 128, true), s, p);
   return rsp_check_launch("wgrad_dma_h16_kernel");
 }
 
-// the 32-row tile with at most 16 live channels: two 16 x 16 blocks per wave (RSP_NO_HALF_BLOCK=1: the 32 x 32 block; read once)
-static bool wgrad_h16(int cout) {
-  static const bool off = getenv("RSP_NO_HALF_BLOCK") != nullptr;
-  return !off && cout <= 16;
-}
+// the 32-row tile with at most 16 live channels: two 16 x 16 blocks per wave ("no_half_block" / RSP_NO_HALF_BLOCK: the 32 x 32 block)
+static bool wgrad_h16(int cout) { return !rsp_conv_option(OPT_NO_HALF_BLOCK) && cout <= 16; }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 int launch_w_vec(const WgradParams& p, bool va, bool vb, hipStream_t s) {
@@ -802,7 +785,7 @@ struct WSkip {
 
 WSkip wgrad_skip_plan(const rsp_conv3d_desc* d, const WPlan& w) {
   WSkip k = {0, 0, 0, 0, 0};
-  static const bool no_skip = getenv("RSP_NO_PAD_SKIP") != nullptr;      // (A/B switch for measurements, read once)
+  const bool no_skip = rsp_conv_option(OPT_NO_PAD_SKIP);      // (A/B switch for measurements)
   k.skip_pad = (!no_skip && d->kT > 1 && d->pT > 0 && d->Ho * d->Wo >= RK) ? 1 : 0;
   const int K = d->kT * d->kH * d->kW * d->Cin;
   // k tiles that skip no frame: those whose kernel depths [kt_lo, kt_hi] reach inside the input for every output frame

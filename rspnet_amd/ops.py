@@ -9,6 +9,7 @@ tensors and the built ``librspnet_hip.so`` and raises otherwise.  ``set_backend`
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes as C
 import functools
 from dataclasses import dataclass
@@ -248,6 +249,26 @@ class HipOps:
         _conv_plan.cache_clear()
         executed_fraction.cache_clear()
         return prev
+
+    @contextlib.contextmanager
+    def options(self, **kw):
+        """Planning options (set_option) for the length of a `with` block: sets each, then restores every one on the way out, an
+        exception included, to what it was before (-1, i.e. the environment or the default, when the call showed no override).
+        Caches: set_option drops the two that hold what the library PLANS per geometry — _conv_plan (kernel names, workspace sizes)
+        and executed_fraction.  The row-geometry tables of _rowgeom_table stay: a table holds input offsets and validity bits per
+        output position, a function of the geometry alone — "no_pad_skip" changes which chunks the kernels walk, not the table —
+        and so do the pack signatures and the grow-only workspaces (sized per call from the fresh plan)."""
+        before = {}
+        try:
+            for name, value in kw.items():
+                prev = self.set_option(name, value)       # the effective value before
+                self.set_option(name, -1)
+                unset = self.set_option(name, value)      # ... and what the environment / the default gives
+                before[name] = -1 if prev == unset else prev      # (prev differs from it only as an override)
+            yield self
+        finally:
+            for name, value in before.items():
+                self.set_option(name, value)
 
     # ---- conv -------------------------------------------------------------------------------------------------
     def conv_pack_fwd(self, g: ConvGeom, w_ref: torch.Tensor) -> torch.Tensor:

@@ -151,6 +151,26 @@ def test_tile_plan_option_changes_the_dispatch_not_the_interface():
     assert lib.rsp_conv3d_set_option(b"no_such_option", 1) == -1 and b"unknown option" in lib.rsp_last_error()
 
 
+# the option table of rsp_conv3d_set_option (csrc/common.h RSP_CONV_OPTIONS): name, environment variable, flag?, built-in default
+CONV_OPTIONS = [("narrow_max_tiles", "RSP_NARROW_MAX_TILES", False, 512), ("narrow32_max_units", "RSP_NARROW32_MAX_UNITS", False, 256),
+                ("tall_min_tiles", "RSP_TALL_MIN_TILES", False, 0), ("two_level_min_chunks", "RSP_TWO_LEVEL_MIN_CHUNKS", False, 0),
+                ("direct_max_tiles", "RSP_DIRECT_MAX_TILES", False, 0), ("no_persist", "RSP_NO_PERSIST", True, 0),
+                ("no_half_block", "RSP_NO_HALF_BLOCK", True, 0), ("no_pad_skip", "RSP_NO_PAD_SKIP", True, 0),
+                ("no_dmajor", "RSP_NO_DMAJOR", True, 0), ("no_tm_skip", "RSP_NO_TM_SKIP", True, 0),
+                ("no_multi_split", "RSP_NO_MULTI_SPLIT", True, 0)]
+
+
+def test_every_conv_option_is_accepted_overridden_and_restored():
+    """Each of the eleven names: its default (in a clean environment; else what the variable says) comes back as the previous
+    effective value, an override is returned by the call that lifts it, and the option is back at its default afterwards."""
+    lib = _lib.load()
+    for name, var, flag, dflt in CONV_OPTIONS:
+        want = dflt if var not in os.environ else (1 if flag else int(os.environ[var] or 0))
+        assert lib.rsp_conv3d_set_option(name.encode(), 7) == want, name
+        assert lib.rsp_conv3d_set_option(name.encode(), -1) == 7, name
+        assert lib.rsp_conv3d_set_option(name.encode(), -1) == want, name
+
+
 def test_no_memset_or_memcpy_nodes_in_the_step_kernels():
     """Round 6: a hipMemsetAsync captured into a LINEAR HIP graph (rspnet_amd/graph_step.py, "lanes") was not reliably ordered against
     the kernels around it on this stack — R3D-18's shortcut input gradients came out wrong in a few replays per hundred

@@ -171,18 +171,12 @@ def test_conv_tall_and_narrow32_instances(hip, case):
     dx_ref = CPU.conv_dgrad(g, dy, w)
     xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
     tall = case in TALL_CASES
-    if tall:
-        hip.set_option("tall_min_tiles", 2)
-        hip.set_option("narrow32_max_units", 0)      # (at these sizes the launch would otherwise count as a tiny one)
-    try:
+    # (narrow32_max_units: at these sizes the launch would otherwise count as a tiny one)
+    with hip.options(**({"tall_min_tiles": 2, "narrow32_max_units": 0} if tall else {})):
         y, st = hip.conv_fwd(g, xd, hip.conv_pack_fwd(g, wd), bd, True)
         kf = hip.lib.rsp_last_conv_kernel().decode()
         dx = hip.conv_dgrad(g, dy.to(DEV), wd)
         kd = hip.lib.rsp_last_conv_kernel().decode()
-    finally:
-        if tall:
-            hip.set_option("tall_min_tiles", -1)
-            hip.set_option("narrow32_max_units", -1)
     close(y, y_ref, 2e-5, "conv fwd")
     close(st.double().sum(0), st_ref.double().sum(0), 2e-5, "stat partials")
     close(dx, dx_ref, 2e-5, "dgrad")
@@ -208,14 +202,11 @@ def test_conv_two_level_summation_instance(hip):
     wp = hip.conv_pack_fwd(g, wd)
     y1, _ = hip.conv_fwd(g, xd, wp, None, True)
     k1 = hip.lib.rsp_last_conv_kernel().decode()
-    hip.set_option("two_level_min_chunks", 8)
-    try:
+    with hip.options(two_level_min_chunks=8):
         y2, st2 = hip.conv_fwd(g, xd, wp, None, True)
         k2 = hip.lib.rsp_last_conv_kernel().decode()
         dx2 = hip.conv_dgrad(g, dy.to(DEV), wd)
         kd = hip.lib.rsp_last_conv_kernel().decode()
-    finally:
-        hip.set_option("two_level_min_chunks", -1)
     assert "fold" not in k1 and "igemm_persist_fold_kernel<128, 128" in k2, (k1, k2, kd)
     close(y2, y_ref, 2e-5, "conv fwd (two-level)")
     close(st2.double().sum(0), st_ref.double().sum(0), 2e-5, "stat partials (two-level)")

@@ -3,10 +3,9 @@
 sizes, executed fractions and stat tiles, under the default planning options and the non-default ones.  ctypes only, no GPU, no torch.
 
     python tools/conv_plan_table.py OUT.json        # the whole table (tests/golden/conv_plan.json was written this way)
-    python tools/conv_plan_table.py --subset        # NAME_CASES + SETS under the default options, JSON on stdout (the environment
-                                                    # switches are read once per process: one child interpreter per switch)
+    python tools/conv_plan_table.py --subset        # NAME_CASES + SETS as planned now (under an RSP_* variable, say), JSON on stdout
 
-tests/test_conv_plan_cpu.py regenerates both from the built library and demands equality with the committed table: a change to the
+tests/test_conv_plan_cpu.py regenerates it from the built library and demands equality with the committed table: a change to the
 planning code that moves any dispatch decision, workspace size or fraction shows up there without a GPU."""
 import ast
 import ctypes as C
@@ -20,8 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # option sets every descriptor is planned under (rsp_conv3d_set_option; -1 restores the default)
 OPTIONS = [{}, {"narrow_max_tiles": 0}, {"narrow32_max_units": 0}, {"tall_min_tiles": 2}, {"tall_min_tiles": 768}, {"two_level_min_chunks": 8}]
-# environment A/B switches, each planned in a child interpreter over the subset
+# A/B switches planned over the subset: (environment variable = key of the table's "env" section, value), and each one's option name
 ENV_SWITCHES = [("RSP_NO_PERSIST", "1"), ("RSP_NO_HALF_BLOCK", "1"), ("RSP_NO_MULTI_SPLIT", "1"), ("RSP_DIRECT_MAX_TILES", "4")]
+SWITCH_OPTIONS = {"RSP_NO_PERSIST": "no_persist", "RSP_NO_HALF_BLOCK": "no_half_block", "RSP_NO_MULTI_SPLIT": "no_multi_split", "RSP_DIRECT_MAX_TILES": "direct_max_tiles"}
 
 # Convolution geometries of the four benchmark workloads at full size (C3D, R3D-18, R(2+1)D-VCOP at batch 32, 16 x 112 x 112; S3D-G at
 # batch 16, 16 x 224 x 224): (N, D, H, W, Cin, Cout, k, s, p, in_ld, out_ld).  The pitches wider than the channel count are S3D-G's
@@ -158,18 +158,23 @@ def plan_rows(lib, mod, cases):
     return rows
 
 
+def planned(lib, mod, cases, opts):      # plan_rows under an option set; the options are back at their defaults afterwards
+    for name, value in opts.items():
+        assert lib.rsp_conv3d_set_option(name.encode(), value) >= 0, name
+    try:
+        return plan_rows(lib, mod, cases)
+    finally:
+        for name in opts:
+            lib.rsp_conv3d_set_option(name.encode(), -1)
+
+
 def table(lib, mod):
     cases = all_cases()
-    out = {"cases": [list(c) for c in cases], "options": OPTIONS, "rows": []}
-    for opts in OPTIONS:
-        for name, value in opts.items():
-            lib.rsp_conv3d_set_option(name.encode(), value)
-        try:
-            out["rows"].append(plan_rows(lib, mod, cases))
-        finally:
-            for name in opts:
-                lib.rsp_conv3d_set_option(name.encode(), -1)
-    return out
+    return {"cases": [list(c) for c in cases], "options": OPTIONS, "rows": [planned(lib, mod, cases, opts) for opts in OPTIONS]}
+
+
+def switch_rows(lib, mod, variable):      # the subset's plan under one of ENV_SWITCHES, set through its option
+    return planned(lib, mod, subset_cases(), {SWITCH_OPTIONS[variable]: int(dict(ENV_SWITCHES)[variable])})
 
 
 def compact(tab):
@@ -189,15 +194,9 @@ if __name__ == "__main__":
     mod = _lib_module()
     lib = mod.load()
     if sys.argv[1:] == ["--subset"]:
-        json.dump(plan_rows(lib, mod, subset_cases()), sys.stdout)
-    else:
-        import subprocess
-        tab = compact(table(lib, mod))
-        tab["env"] = {}
-        for name, value in ENV_SWITCHES:
-            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--subset"], env=dict(os.environ, **{name: value}),
-                                 check=True, capture_output=True, text=True)
-            tab["env"][name] = json.loads(res.stdout)
-        with open(sys.argv[1], "w") as f:
-            json.dump(tab, f, separators=(",", ":"))
-            f.write("\n")
+        sys.exit(json.dump(plan_rows(lib, mod, subset_cases()), sys.stdout))
+    tab = compact(table(lib, mod))
+    tab["env"] = {variable: switch_rows(lib, mod, variable) for variable, _ in ENV_SWITCHES}
+    with open(sys.argv[1], "w") as f:
+        json.dump(tab, f, separators=(",", ":"))
+        f.write("\n")

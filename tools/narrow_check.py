@@ -1,9 +1,8 @@
 #!/usr/bin/env python
 """Do the 64-wide tiles (narrow_tiles) change a convolution's output by more than summation-order noise?  The same forward (+ BN
-statistic partials) and input gradient in two child interpreters — default and RSP_NARROW_MAX_TILES=0 — compared against an fp64
+statistic partials) and input gradient under the default plan and under the "narrow_max_tiles" = 0 option, compared against an fp64
 reference on the CPU: both must sit at the same distance from it."""
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,11 +11,14 @@ import torch
 
 CASES = [(2, 4, 10, 10, 128, 288, (1, 3, 3)), (4, 2, 7, 7, 256, 256, (3, 3, 3)), (2, 4, 14, 14, 480, 400, (1, 1, 1)),
          (4, 4, 8, 8, 64, 128, (3, 3, 3)), (4, 1, 4, 4, 512, 512, (3, 3, 3))]
-if len(sys.argv) > 1 and sys.argv[1] == "child":
-    from rspnet_amd import ops
-    from rspnet_amd.ops import ConvGeom
-    be = ops.backend()
-    dev = torch.device("cuda", 0)
+from rspnet_amd import ops
+from rspnet_amd.ops import ConvGeom
+
+be = ops.backend()
+dev = torch.device("cuda", 0)
+
+
+def run():
     out = {}
     for i, (N, D, H, W, cin, cout, k) in enumerate(CASES):
         g0 = torch.Generator().manual_seed(100 + i)
@@ -28,13 +30,13 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
         dy = torch.randn(y.shape, generator=g0)
         dx = be.conv_dgrad(g, dy.to(dev), w.to(dev))
         out[i] = (y.cpu(), st.double().sum(0).cpu(), dx.cpu(), be.lib.rsp_last_conv_kernel().decode())
-    torch.save(out, sys.argv[2])
-    sys.exit(0)
+    return out
+
+
 res = {}
-for tag, env in (("narrow", {}), ("wide", {"RSP_NARROW_MAX_TILES": "0"})):
-    path = f"/tmp/narrow_check_{tag}.pt"
-    subprocess.run([sys.executable, os.path.abspath(__file__), "child", path], check=True, env=dict(os.environ, **env))
-    res[tag] = torch.load(path)
+for tag, opts in (("narrow", {}), ("wide", {"narrow_max_tiles": 0})):
+    with be.options(**opts):
+        res[tag] = run()
 for i, (N, D, H, W, cin, cout, k) in enumerate(CASES):
     g0 = torch.Generator().manual_seed(100 + i)
     x = torch.randn(N, D, H, W, cin, generator=g0)
