@@ -3,11 +3,12 @@
 A backbone (rspnet_amd/models/*) is an ``nn.Module`` tree that only *holds* parameters under the reference's
 state-dict names; its ``plan()`` lists fused units over numbered tensor slots:
 
-  ConvBN   conv3d → BatchNorm3d(train) [→ + residual] [→ ReLU] [→ disjoint MaxPool3d]     (all four backbones)
-  ConvBias conv3d + bias [→ ReLU], no BatchNorm                                            ('conv' projection head)
-  Pool     stand-alone MaxPool3d with overlapping windows                                  (ResNet stem, S3D-G)
-  Gate     S3D-G self-gating  x * sigmoid(W·mean(x) + b)
-  Concat   channel concat of branch outputs (S3D-G inception)
+  ConvBN      conv3d → BatchNorm3d [→ + residual] [→ ReLU] [→ disjoint MaxPool3d]             (all four backbones)
+  ConvBNGroup ConvBN units that read one tensor with one geometry: one GEMM over their filters   (S3D-G inception siblings)
+  ConvBias    conv3d + bias [→ ReLU], no BatchNorm                                              ('conv' projection head)
+  Pool        stand-alone MaxPool3d with overlapping windows                                    (ResNet stem, S3D-G)
+  Gate        S3D-G self-gating  x * sigmoid(W·mean(x) + b)
+A channel concat (S3D-G inception) is no node: the branches' last units write channel slices of one tensor (`into`).
 
 Forward keeps, per ConvBN, only the conv input, the raw conv output y and the per-channel (mean, invstd, scale,
 shift); the activation / ReLU mask / pool arg-max are recomputed from y in backward.
@@ -18,7 +19,7 @@ from __future__ import annotations
 import contextlib
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 import torch
 from torch import nn
@@ -59,18 +60,7 @@ class ConvBNGroup:
     stays per member (channel slices of the shared conv output / statistics).  With any other parameter layout (fine-tune
     path, stand-alone use) the members simply run one by one."""
     members: List[ConvBN]
-
-    def _cat_node(self):
-        """What PackedWeights keys on: an object whose .conv.weight is the concatenated filter tensor."""
-        holder = getattr(self, "_holder", None)
-        if holder is None:
-            holder = self._holder = _CatHolder(self._cat)
-        return holder
-
-
-class _CatHolder:
-    def __init__(self, conv):
-        self.conv = conv
+    cat: Optional["_CatConv"] = field(default=None, repr=False, compare=False)      # what PackedWeights keys on: holds the concatenated filters
 
 
 @dataclass
@@ -111,6 +101,8 @@ class Plan:
     nodes: List[object]
     input_slot: int = 0
     output_slot: int = 0
+    gate_fusion: Optional[dict] = field(default=None, repr=False, compare=False)      # cached tables of _gate_fusion /
+    pool_fusion: Optional[dict] = field(default=None, repr=False, compare=False)      # _pool_fusion, built at the first use
 
 
 @dataclass
@@ -123,13 +115,31 @@ class _Saved:
     pg: PoolGeom
     res: Optional[torch.Tensor] = None
     eval_mode: bool = False                        # BatchNorm ran on its running statistics: mi is _eval_mean_invstd's
+    gate: Optional["_SavedGate"] = None            # the self-gating unit fused behind this BatchNorm (_gate_fusion): one backward op
+
+
+# What the other node kinds' backwards need, one record type per kind (ForwardCtx.saved).  _SavedVStem: a ConvBN that ran as two
+# convolutions over virtual pixels (VirtualStem); _SavedGroup: a ConvBNGroup that ran as ONE GEMM — `per` holds, per member, its
+# channel slice [off, off + C) of the shared convolution output and its BatchNorm vectors (a group whose members ran one by one keeps
+# a _Saved per member, keyed (index, j)); _SavedGate: `at` = plan index of the Gate node, `x` = what the gate multiplied — None when it
+# ran fused behind a ConvBN (_gate_fusion): that ConvBN's _Saved.gate is this record too, and its backward recomputes the activation
+_SavedVStem = NamedTuple("_SavedVStem", [("x_e", torch.Tensor), ("x_o", torch.Tensor), ("y", torch.Tensor), ("mi", torch.Tensor),
+                                         ("ss", torch.Tensor), ("cg", ConvGeom), ("pg", PoolGeom), ("vs", "VirtualStem")])
+_SavedMember = NamedTuple("_SavedMember", [("off", int), ("C", int), ("mi", torch.Tensor), ("ss", torch.Tensor), ("pg", PoolGeom)])
+_SavedGroup = NamedTuple("_SavedGroup", [("x", torch.Tensor), ("y", torch.Tensor), ("cg", ConvGeom), ("per", List[_SavedMember])])
+_SavedPool = NamedTuple("_SavedPool", [("pg", PoolGeom), ("idx", torch.Tensor)])      # idx: arg-max
+_SavedGate = NamedTuple("_SavedGate", [("at", int), ("x", Optional[torch.Tensor]), ("mean", torch.Tensor), ("gate", torch.Tensor)])
+_SavedConvBias = NamedTuple("_SavedConvBias", [("x", torch.Tensor), ("y", torch.Tensor), ("cg", ConvGeom)])
+SavedState = Union[_Saved, _SavedVStem, _SavedGroup, _SavedPool, _SavedGate, _SavedConvBias]
 
 
 @dataclass
 class ForwardCtx:
-    saved: Dict[int, _Saved] = field(default_factory=dict)
+    # plan index (or (group index, member) where a group ran its members one by one) -> what that node's backward needs
+    saved: Dict[Union[int, Tuple[int, int]], SavedState] = field(default_factory=dict)
     feat_shape: Optional[Tuple[int, ...]] = None
     packed: Optional["PackedWeights"] = None       # the encoder's weight cache (dgrad layouts are fetched from it in backward)
+    head: object = None                            # the projection heads' saved state (moco/split_wrapper.py)
 
 
 class PackedWeights:
@@ -186,11 +196,18 @@ class PackedWeights:
             at = self._index[key] = (len(self._sets) - 1, 0)
         return self._sets[at[0]].packed[at[1]]
 
-    def get(self, node, cg: ConvGeom):
-        return self._lookup(node.conv, cg, 0)
+    def get(self, conv, cg: ConvGeom):
+        """conv: whatever holds `.weight` — a conv module, a group's _CatConv, a VirtualStem holder."""
+        return self._lookup(conv, cg, 0)
 
-    def get_dgrad(self, node, cg: ConvGeom):
-        return self._lookup(node.conv, cg, 1)
+    def get_dgrad(self, conv, cg: ConvGeom):
+        return self._lookup(conv, cg, 1)
+
+    def virtual_stem(self, node) -> "VirtualStem":
+        vs = self._virtual.get(id(node.conv))
+        if vs is None or vs.device != node.conv.weight.device:
+            vs = self._virtual[id(node.conv)] = VirtualStem(node)
+        return vs
 
 
 class _CatConv:
@@ -212,12 +229,6 @@ def _adjacent_cat(ts):
     shape = (sum(t.shape[0] for t in ts),) + tuple(t0.shape[1:])
     stride = tuple(t0.stride())
     return torch.as_strided(t0, shape, stride, t0.storage_offset())
-
-
-def _pad_vec(v: torch.Tensor, n: int, fill: float = 0.0) -> torch.Tensor:
-    out = torch.full((n,), fill, dtype=v.dtype, device=v.device)
-    out[:v.shape[0]] = v
-    return out
 
 
 INPUT_CHANNEL_PAD = 4
@@ -260,7 +271,7 @@ class VirtualStem:
             self.dst.append(real.reshape(-1)[flat_valid].to(w.device))
             h = _CatConv()
             h.weight = torch.zeros((Cout, 4, kT, kH, 6), dtype=w.dtype, device=w.device)
-            self.holders.append(_CatHolder(h))
+            self.holders.append(h)
         self.device = w.device
         self.refresh()
 
@@ -280,7 +291,7 @@ class VirtualStem:
         w = self.conv.weight
         ext = torch.cat([w.data.reshape(-1), w.data.new_zeros(1)])
         for h, idx in zip(self.holders, self.idx):
-            torch.index_select(ext, 0, idx, out=h.conv.weight.view(-1))
+            torch.index_select(ext, 0, idx, out=h.weight.view(-1))
 
     def pack_rows(self, xin):
         """(N,D,H,W,4) clip with a zero 4th channel -> packed 3-channel rows as virtual pixels: (N,D,H,Wv+5,4) for the even outputs and
@@ -437,19 +448,24 @@ class BranchStreams:
             self.join_task()
 
 
-def _gate_fusion(plan: "Plan"):
-    """{index of a ConvBN: (index of the Gate that is the only reader of its output, index of the Pool that is the only reader of
-    the gate's output | None)} — S3D-G's sep_conv units (models/s3dg.py:36-72) and, for the two front-end ones, the max-pool
-    behind them (:105-109).  The three run as one op (ops.bn_act_gate_fwd)."""
-    cached = getattr(plan, "_gate_fusion", None)
-    if cached is not None:
-        return cached
+def _readers(plan: "Plan") -> Dict[int, List[int]]:
+    """{slot: indices of the plan nodes that read it, as input or as residual}"""
     readers: Dict[int, List[int]] = {}
     for i, n in enumerate(plan.nodes):
         for m in (n.members if isinstance(n, ConvBNGroup) else [n]):
             for slot in (getattr(m, "src", None), getattr(m, "residual", None)):
                 if slot is not None:
                     readers.setdefault(slot, []).append(i)
+    return readers
+
+
+def _gate_fusion(plan: "Plan"):
+    """{index of a ConvBN: (index of the Gate that is the only reader of its output, index of the Pool that is the only reader of
+    the gate's output | None)} — S3D-G's sep_conv units (models/s3dg.py:36-72) and, for the two front-end ones, the max-pool
+    behind them (:105-109).  The three run as one op (ops.bn_act_gate_fwd)."""
+    if plan.gate_fusion is not None:
+        return plan.gate_fusion
+    readers = _readers(plan)
     table = {}
     if not os.environ.get("RSP_NO_GATE_FUSION"):
         for i, n in enumerate(plan.nodes[:-1]):
@@ -467,7 +483,7 @@ def _gate_fusion(plan: "Plan"):
                         and g.dst != plan.output_slot):
                     pi = i + 2
             table[i] = (i + 1, pi)
-    plan._gate_fusion = table
+    plan.gate_fusion = table
     return table
 
 
@@ -479,15 +495,9 @@ def _pool_fusion(plan: "Plan"):
     MaxPool3d(3, 2, 1), models/resnet.py:124-139,203-207).  A forward that keeps nothing for a backward (the two key passes) applies
     the BatchNorm and takes the window maximum in ONE pass over the convolution output (rsp_bn_act_pool_fwd takes any window): the
     activated tensor — 411 MB per pass on R3D-18 — is neither written nor read back.  Same arithmetic per element, same bits."""
-    cached = getattr(plan, "_pool_fusion", None)
-    if cached is not None:
-        return cached
-    readers: Dict[int, List[int]] = {}
-    for i, n in enumerate(plan.nodes):
-        for m in (n.members if isinstance(n, ConvBNGroup) else [n]):
-            for slot in (getattr(m, "src", None), getattr(m, "residual", None)):
-                if slot is not None:
-                    readers.setdefault(slot, []).append(i)
+    if plan.pool_fusion is not None:
+        return plan.pool_fusion
+    readers = _readers(plan)
     table = {}
     if not os.environ.get("RSP_NO_POOL_FUSION"):
         gated = _gate_fusion(plan)
@@ -498,20 +508,24 @@ def _pool_fusion(plan: "Plan"):
             if n.pool or n.into is not None or n.cout_pad or n.dst == plan.output_slot or readers.get(n.dst) != [i + 1]:
                 continue
             table[i] = i + 1
-    plan._pool_fusion = table
+    plan.pool_fusion = table
     return table
 
 
-def _slice_of(slots, into, lead_shape, device):
-    """Channel-slice view of a concat tensor, allocating the tensor on first use."""
+# ---- helpers of both directions ----------------------------------------------------------------------------------------
+def _view(t, into, C):
+    return t if into is None else t[..., into[1]:into[1] + C]
+
+
+def _out_view(slots, into, lead_shape, C, device):
+    """Where a node with `into` = (concat slot, channel offset, total channels) writes: its channel slice of the concat tensor,
+    which is allocated on first use.  None without `into`: the op allocates its output, and the caller puts it into the node's slot."""
+    if into is None:
+        return None
     slot, off, total = into
     if slot not in slots:
         slots[slot] = torch.empty(tuple(lead_shape) + (total,), dtype=torch.float32, device=device)
-    return slots[slot]
-
-
-def _view(t, into, C):
-    return t if into is None else t[..., into[1]:into[1] + C]
+    return _view(slots[slot], into, C)
 
 
 def _eval_scale_shift(bn, bias) -> torch.Tensor:
@@ -535,68 +549,70 @@ EVAL_BACKWARD_MISSING = ("backward through an eval-mode backbone (BatchNorm on r
                          "freeze the backbone (only_train_fc) or call model.train()")
 
 
-def run_forward(plan: Plan, x: torch.Tensor, packed: PackedWeights, keep: bool, training: bool = True,
-                deferred: Optional[Dict[int, torch.Tensor]] = None) -> Tuple[torch.Tensor, Optional[ForwardCtx]]:
-    """Execute `plan` on x (N,D,H,W,C).  keep=True records what backward needs.  training=True: batch-statistics BN (the
-    pretext step never runs anything else: pretrain.py:225); training=False: running-statistics BN for the fine-tune /
-    validation forward (finetune.py:333-345) and for fine-tuning with frozen BatchNorm (keep=True: the backward then runs
-    bn_eval_act_pool_bwd per ConvBN; no virtual stem, no grouped convolutions, no gate fusion in this mode, so Gate and Pool nodes
-    keep their ordinary saved state)."""
-    be = _ops.backend()
+def _handler(table, node):
+    fn = table.get(type(node))
+    if fn is None:
+        raise NotImplementedError(f"plan node {type(node).__name__}")
+    return fn
 
-    def finalize(bn, stats, rows, bias_d):
+
+class _Forward:
+    """One forward through a plan: the state run_forward's node handlers share, and one handler per node type."""
+
+    def __init__(self, plan, x, packed, keep, training, deferred):
+        self.be = _ops.backend()
+        self.plan, self.packed, self.keep, self.training, self.deferred = plan, packed, keep, training, deferred
+        self.slots: Dict[int, torch.Tensor] = {plan.input_slot: x}
+        self.ctx = ForwardCtx(packed=packed) if keep else None
+        self.pool_fusion = _pool_fusion(plan)
+        self.gate_fusion = _gate_fusion(plan) if training else {}
+        self.skipped = set()        # nodes that ran inside the kernel of the ConvBN in front of them
+
+    def finalize(self, bn, stats, rows, bias_d):
         # deferred: {id(BatchNorm module): [2][C] buffer} — this pass reports its batch moments there and leaves the running
         # statistics to a later rsp_bn_running_update (ops.BnEmaSet); otherwise bn_finalize moves them itself
-        bso = deferred.get(id(bn)) if deferred is not None else None
+        bso = self.deferred.get(id(bn)) if self.deferred is not None else None
         if bso is not None:
-            return be.bn_finalize(stats, rows, bias_d, bn.weight.data, bn.bias.data, float(bn.eps), float(bn.momentum), None, None,
-                                  batch_stats_out=bso)
-        return be.bn_finalize(stats, rows, bias_d, bn.weight.data, bn.bias.data, float(bn.eps), float(bn.momentum),
-                              bn.running_mean, bn.running_var)
+            return self.be.bn_finalize(stats, rows, bias_d, bn.weight.data, bn.bias.data, float(bn.eps), float(bn.momentum), None, None,
+                                       batch_stats_out=bso)
+        return self.be.bn_finalize(stats, rows, bias_d, bn.weight.data, bn.bias.data, float(bn.eps), float(bn.momentum),
+                                   bn.running_mean, bn.running_var)
 
-    slots: Dict[int, torch.Tensor] = {plan.input_slot: x}
-    ctx = ForwardCtx(packed=packed) if keep else None
-    pool_fusion = _pool_fusion(plan)
-    skipped = set()
-
-    def bn_apply(node, y, ss, cg_cout, N, do, ho, wo, xin, key=None):
+    def bn_apply(self, node, y, ss, C, dims, xin, key=None):
+        """BatchNorm apply [+ residual] [+ ReLU] [+ pool] of a convolution output y with `C` channels and dims (N, do, ho, wo)
+        -> (PoolGeom a backward needs, residual)."""
+        be, slots = self.be, self.slots
         pk, ps = node.pool if node.pool else ((1, 1, 1), (1, 1, 1))
-        pg = PoolGeom(N, do, ho, wo, cg_cout, pk, ps, (0, 0, 0))
+        pg = PoolGeom(*dims, C, pk, ps, (0, 0, 0))
         res = slots[node.residual] if node.residual is not None else None
-        pi = pool_fusion.get(key) if key is not None else None
+        pi = self.pool_fusion.get(key) if key is not None else None
         if pi is not None:      # the max-pool behind this unit taken by the kernel that applies the BatchNorm (_pool_fusion)
-            pnode = plan.nodes[pi]
-            pgf = PoolGeom(N, do, ho, wo, cg_cout, pnode.k, pnode.s, pnode.p)
-            if not keep:
+            pnode = self.plan.nodes[pi]
+            pgf = PoolGeom(*dims, C, pnode.k, pnode.s, pnode.p)
+            if not self.keep:
                 slots[pnode.dst] = be.bn_act_pool_fwd(pgf, y, ss, res, node.relu)
-                skipped.add(pi)
+                self.skipped.add(pi)
                 return pgf, res
             # kept for a backward: the same pass also writes the arg-max (the Pool node's saved state); the BatchNorm backward
             # recomputes the activation from y as everywhere, so the activated tensor is never materialised
             fused = be.bn_act_maxpool_fwd(pgf, y, ss, node.relu, True) if (res is None and hasattr(be, "bn_act_maxpool_fwd")) else None
             if fused is not None:
                 slots[pnode.dst], idx = fused
-                ctx.saved[pi] = (pgf, idx)
-                skipped.add(pi)
+                self.ctx.saved[pi] = _SavedPool(pgf, idx)
+                self.skipped.add(pi)
                 return pg, res
-        if node.into is not None:
-            pdo, pho, pwo = pg.out_dims
-            out = _view(_slice_of(slots, node.into, (N, pdo, pho, pwo), xin.device), node.into, cg_cout)
+        out = _out_view(slots, node.into, (dims[0],) + pg.out_dims, C, xin.device)
+        if out is not None:
             be.bn_act_pool_fwd(pg, y, ss, res, node.relu, out=out)
         else:
             slots[node.dst] = be.bn_act_pool_fwd(pg, y, ss, res, node.relu)
         return pg, res
 
-    def convbn_virtual(node, key):
+    def convbn_virtual(self, node, key, xin):
         """ConvBN of a 3-channel stride-2 stem as two ordinary convolutions over virtual pixels (see VirtualStem)."""
-        xin = slots[node.src]
         N, D, H, W, _ = xin.shape
-        w = node.conv.weight
-        Cout = w.shape[0]
-        Cp = node.cout_pad if node.cout_pad > Cout else Cout
-        vs = packed._virtual.get(id(node.conv))
-        if vs is None or vs.device != w.device:
-            vs = packed._virtual[id(node.conv)] = VirtualStem(node)
+        Cp = max(node.cout_pad, node.conv.weight.shape[0])
+        vs = self.packed.virtual_stem(node)
         x_e, x_o = vs.pack_rows(xin)
         (kT, kH, _), (sT, sH, _), (pT, pH, _) = node.k, node.s, node.p
         cg = ConvGeom(N, D, H, x_e.shape[3], 4, Cp, (kT, kH, 6), (sT, sH, 3), (pT, pH, 0), Cin_alg=3 * 7 / 6)
@@ -605,155 +621,158 @@ def run_forward(plan: Plan, x: torch.Tensor, packed: PackedWeights, keep: bool, 
         yv = y.view(N, do, ho, g, 2 * Cp)
         parts = []
         for c, xc in enumerate((x_e, x_o)):
-            _, st = be.conv_fwd(cg, xc, packed.get(vs.holders[c], cg), None, True, out=yv[..., c * Cp:(c + 1) * Cp], out_ld=2 * Cp)
+            _, st = self.be.conv_fwd(cg, xc, self.packed.get(vs.holders[c], cg), None, True, out=yv[..., c * Cp:(c + 1) * Cp], out_ld=2 * Cp)
             parts.append(st)
         rows = N * do * ho * 2 * g
-        mi, ss = finalize(node.bn, torch.cat(parts), rows, None)
-        pg, res, = bn_apply(node, y, ss, Cp, N, do, ho, 2 * g, xin, key)
-        if keep:
-            ctx.saved[key] = ("vstem", x_e, x_o, y, mi, ss, cg, pg, vs)
+        mi, ss = self.finalize(node.bn, torch.cat(parts), rows, None)
+        pg, _ = self.bn_apply(node, y, ss, Cp, (N, do, ho, 2 * g), xin, key)
+        if self.keep:
+            self.ctx.saved[key] = _SavedVStem(x_e, x_o, y, mi, ss, cg, pg, vs)
 
-    def convbn(node, key, gated=None):
-        xin = slots[node.src]
-        if training and node.virtual_w and VirtualStem.applies(node, xin):
-            return convbn_virtual(node, key)
+    def convbn(self, node, key):
+        be, keep = self.be, self.keep
+        xin = self.slots[node.src]
+        if self.training and node.virtual_w and VirtualStem.applies(node, xin):
+            return self.convbn_virtual(node, key, xin)
         N, D, H, W, Cin = xin.shape
         w = node.conv.weight
         Cout = w.shape[0]
-        Cp = node.cout_pad if node.cout_pad > Cout else Cout
+        Cp = max(node.cout_pad, Cout)
         cg = ConvGeom(N, D, H, W, Cin, Cp, node.k, node.s, node.p, Cin_alg=w.shape[1])
         bias = getattr(node.conv, "bias", None)
         bn = node.bn
         bias_d = None if bias is None else bias.data
-        if training:
+        if self.training:
             # (no shipped backbone has a conv bias on channel-padded units; if one does, the conv needs it at the padded length)
-            bias_conv = bias_d if (bias_d is None or Cp == Cout) else _pad_vec(bias_d, Cp)
-            y, stats = be.conv_fwd(cg, xin, packed.get(node, cg), bias_conv, True)
+            bias_conv = bias_d if (bias_d is None or Cp == Cout) else torch.cat([bias_d, bias_d.new_zeros(Cp - Cout)])
+            y, stats = be.conv_fwd(cg, xin, self.packed.get(node.conv, cg), bias_conv, True)
             # (zero-padded output channels, Cp > Cout: the BatchNorm vectors keep their Cout entries, the kernels treat the rest
             #  as gamma = beta = 0 and leave the running statistics of the real channels alone)
-            mi, ss = finalize(bn, stats, cg.rows, bias_d)
+            mi, ss = self.finalize(bn, stats, cg.rows, bias_d)
         else:
-            y, _ = be.conv_fwd(cg, xin, packed.get(node, cg), None, False)     # bias folded into the shift
+            y, _ = be.conv_fwd(cg, xin, self.packed.get(node.conv, cg), None, False)     # bias folded into the shift
             ss = _eval_scale_shift(bn, bias)
             mi = _eval_mean_invstd(bn, bias) if keep else None
             if Cp != Cout:
-                ss = torch.cat([ss, torch.zeros((2, Cp - Cout), dtype=ss.dtype, device=ss.device)], dim=1).contiguous()
-                if mi is not None:
-                    mi = torch.cat([mi, torch.zeros((2, Cp - Cout), dtype=mi.dtype, device=mi.device)], dim=1).contiguous()
-        do, ho, wo = cg.out_dims
+                pad = torch.zeros((2, Cp - Cout), dtype=ss.dtype, device=ss.device)
+                ss, mi = (None if v is None else torch.cat([v, pad], dim=1).contiguous() for v in (ss, mi))
+        dims = (N,) + cg.out_dims
+        gated = self.gate_fusion.get(key)
         if gated is not None:
-            # BatchNorm-apply + self-gating (+ the max-pool behind a front-end unit, when nothing is kept for a backward) in two
-            # passes over y: see _gate_fusion
-            gi, pi = gated
-            gnode = plan.nodes[gi]
-            pnode = plan.nodes[pi] if pi is not None else None
-            pg = PoolGeom(N, do, ho, wo, cg.Cout)
-            pool = PoolGeom(N, do, ho, wo, cg.Cout, pnode.k, pnode.s, pnode.p) if pnode is not None else None
-            # (a backward recomputes the activation from y: nothing but the (sample, channel) means and gates is kept)
-            keep_act = keep and not GATE_BWD_FUSED
-            # a forward a backward follows pools in the same pass only if that pass can also write the pool's arg-max
-            with_idx = (keep and pool is not None and not keep_act and getattr(be, "gate_pool_keep", False) and not GATE_POOL_APART
-                        and be.bn_act_gate_pool_idx_ok(pool, y, ss))
-            if keep and not with_idx:
-                pnode = pool = None
-            out = None
-            if gnode.into is not None:
-                out = _view(_slice_of(slots, gnode.into, (N, do, ho, wo), xin.device), gnode.into, cg.Cout)
-            if with_idx:
-                o, a, mean, gate, idx = be.bn_act_gate_fwd(pg, y, ss, node.relu, gnode.conv.weight.data, gnode.conv.bias.data, False,
-                                                           pool=pool, out=out, pool_idx=True)
-                ctx.saved[pi] = (pool, idx)
-            else:
-                o, a, mean, gate = be.bn_act_gate_fwd(pg, y, ss, node.relu, gnode.conv.weight.data, gnode.conv.bias.data, keep_act,
-                                                      pool=pool, out=out)
-            if pnode is not None:
-                slots[pnode.dst] = o
-                skipped.add(pi)
-            elif gnode.into is None:
-                slots[gnode.dst] = o
-            skipped.add(gi)
-            if keep:
-                ctx.saved[key] = _Saved(xin, y, mi, ss, cg, pg, None)
-                ctx.saved[gi] = (a, mean, gate) if keep_act else ("fused", key, mean, gate)
-            return
-        pg, res = bn_apply(node, y, ss, cg.Cout, N, do, ho, wo, xin, key)
+            return self.bn_gate(node, key, gated, xin, y, mi, ss, cg, dims)
+        pg, res = self.bn_apply(node, y, ss, cg.Cout, dims, xin, key)
         if keep:
-            ctx.saved[key] = _Saved(xin, y, mi, ss, cg, pg, res, eval_mode=not training)
+            self.ctx.saved[key] = _Saved(xin, y, mi, ss, cg, pg, res, eval_mode=not self.training)
 
-    def convbn_group(node, ni):
+    def bn_gate(self, node, key, gated, xin, y, mi, ss, cg, dims):
+        """The rest of a ConvBN with the Gate behind it: BatchNorm-apply + self-gating (+ the max-pool behind a front-end unit, when
+        nothing is kept for a backward) in two passes over y: see _gate_fusion"""
+        be, keep, slots = self.be, self.keep, self.slots
+        gi, pi = gated
+        gnode = self.plan.nodes[gi]
+        pnode = self.plan.nodes[pi] if pi is not None else None
+        pg = PoolGeom(*dims, cg.Cout)
+        pool = PoolGeom(*dims, cg.Cout, pnode.k, pnode.s, pnode.p) if pnode is not None else None
+        # (a backward recomputes the activation from y: nothing but the (sample, channel) means and gates is kept)
+        keep_act = keep and not GATE_BWD_FUSED
+        # a forward a backward follows pools in the same pass only if that pass can also write the pool's arg-max
+        with_idx = (keep and pool is not None and not keep_act and getattr(be, "gate_pool_keep", False) and not GATE_POOL_APART
+                    and be.bn_act_gate_pool_idx_ok(pool, y, ss))
+        if keep and not with_idx:
+            pnode = pool = None
+        out = _out_view(slots, gnode.into, dims, cg.Cout, xin.device)
+        gw, gb = gnode.conv.weight.data, gnode.conv.bias.data
+        if with_idx:
+            o, a, mean, gate, idx = be.bn_act_gate_fwd(pg, y, ss, node.relu, gw, gb, False, pool=pool, out=out, pool_idx=True)
+            self.ctx.saved[pi] = _SavedPool(pool, idx)
+        else:
+            o, a, mean, gate = be.bn_act_gate_fwd(pg, y, ss, node.relu, gw, gb, keep_act, pool=pool, out=out)
+        if pnode is not None:
+            slots[pnode.dst] = o
+            self.skipped.add(pi)
+        elif gnode.into is None:
+            slots[gnode.dst] = o
+        self.skipped.add(gi)
+        if keep:
+            sg = self.ctx.saved[gi] = _SavedGate(gi, a if keep_act else None, mean, gate)
+            self.ctx.saved[key] = _Saved(xin, y, mi, ss, cg, pg, None, gate=None if keep_act else sg)
+
+    def group(self, node, ni):
         """One GEMM over the members' concatenated filters (see ConvBNGroup); falls back to member-by-member execution."""
         ms = node.members
-        wcat = _adjacent_cat([m.conv.weight.data for m in ms]) if training else None
+        wcat = _adjacent_cat([m.conv.weight.data for m in ms]) if self.training else None
         if wcat is None:
             for j, m in enumerate(ms):
-                convbn(m, (ni, j))
+                self.convbn(m, (ni, j))
             return
-        xin = slots[ms[0].src]
+        xin = self.slots[ms[0].src]
         N, D, H, W, Cin = xin.shape
-        if getattr(node, "_cat", None) is None:
-            node._cat = _CatConv()
-        node._cat.weight = wcat
+        if node.cat is None:
+            node.cat = _CatConv()
+        node.cat.weight = wcat
         cg = ConvGeom(N, D, H, W, Cin, wcat.shape[0], ms[0].k, ms[0].s, ms[0].p)
-        y, stats = be.conv_fwd(cg, xin, packed.get(node._cat_node(), cg), None, True)
-        do, ho, wo = cg.out_dims
+        y, stats = self.be.conv_fwd(cg, xin, self.packed.get(node.cat, cg), None, True)
         off, per = 0, []
         for m in ms:
             C = m.conv.weight.shape[0]
-            bn = m.bn
-            mi, ss = finalize(bn, stats[:, off:off + C], cg.rows, None)
-            pg, _ = bn_apply(m, y[..., off:off + C], ss, C, N, do, ho, wo, xin)
-            per.append((off, C, mi, ss, pg))
+            mi, ss = self.finalize(m.bn, stats[:, off:off + C], cg.rows, None)
+            pg, _ = self.bn_apply(m, y[..., off:off + C], ss, C, (N,) + cg.out_dims, xin)
+            per.append(_SavedMember(off, C, mi, ss, pg))
             off += C
-        if keep:
-            ctx.saved[ni] = ("group", xin, y, cg, per)
+        if self.keep:
+            self.ctx.saved[ni] = _SavedGroup(xin, y, cg, per)
 
-    fusion = _gate_fusion(plan) if training else {}
+    def convbias(self, node, ni):
+        xin = self.slots[node.src]
+        N, D, H, W, Cin = xin.shape
+        cg = ConvGeom(N, D, H, W, Cin, node.conv.weight.shape[0], node.k, node.s, node.p)
+        y, _ = self.be.conv_fwd(cg, xin, self.packed.get(node.conv, cg), node.conv.bias.data, False)
+        if node.relu:
+            y = self.be.eltwise("relu_fwd", y, out=y)
+        self.slots[node.dst] = y
+        if self.keep:
+            self.ctx.saved[ni] = _SavedConvBias(xin, y, cg)
 
-    def run_node(ni, node):
-        if ni in skipped:
-            return
-        if isinstance(node, ConvBN):
-            convbn(node, ni, fusion.get(ni))
-        elif isinstance(node, ConvBNGroup):
-            convbn_group(node, ni)
-        elif isinstance(node, ConvBias):
-            xin = slots[node.src]
-            N, D, H, W, Cin = xin.shape
-            w = node.conv.weight
-            cg = ConvGeom(N, D, H, W, Cin, w.shape[0], node.k, node.s, node.p)
-            y, _ = be.conv_fwd(cg, xin, packed.get(node, cg), node.conv.bias.data, False)
-            if node.relu:
-                y = be.eltwise("relu_fwd", y, out=y)
-            slots[node.dst] = y
-            if keep:
-                ctx.saved[ni] = (xin, y, cg)
-        elif isinstance(node, Pool):
-            xin = slots[node.src]
-            N, D, H, W, Cc = xin.shape
-            pg = PoolGeom(N, D, H, W, Cc, node.k, node.s, node.p)
-            slots[node.dst], idx = be.maxpool_fwd(pg, xin, keep)
-            if keep:
-                ctx.saved[ni] = (pg, idx)
-        elif isinstance(node, Gate):
-            xin = slots[node.src]
-            out = (_view(_slice_of(slots, node.into, tuple(xin.shape[:4]), xin.device), node.into, xin.shape[4])
-                   if node.into is not None else None)
-            o, mean, gate = be.gate_fwd(xin, node.conv.weight.data, node.conv.bias.data, out=out)
-            if node.into is None:
-                slots[node.dst] = o
-            if keep:
-                ctx.saved[ni] = (xin, mean, gate)
-        else:
-            raise NotImplementedError(f"plan node {type(node).__name__}")
+    def pool(self, node, ni):
+        xin = self.slots[node.src]
+        N, D, H, W, Cc = xin.shape
+        pg = PoolGeom(N, D, H, W, Cc, node.k, node.s, node.p)
+        self.slots[node.dst], idx = self.be.maxpool_fwd(pg, xin, self.keep)
+        if self.keep:
+            self.ctx.saved[ni] = _SavedPool(pg, idx)
 
+    def gate(self, node, ni):
+        xin = self.slots[node.src]
+        out = _out_view(self.slots, node.into, tuple(xin.shape[:4]), xin.shape[4], xin.device)
+        o, mean, gate = self.be.gate_fwd(xin, node.conv.weight.data, node.conv.bias.data, out=out)
+        if node.into is None:
+            self.slots[node.dst] = o
+        if self.keep:
+            self.ctx.saved[ni] = _SavedGate(ni, xin, mean, gate)
+
+    HANDLERS = {ConvBN: convbn, ConvBNGroup: group, ConvBias: convbias, Pool: pool, Gate: gate}
+
+    def run_node(self, ni, node):
+        if ni not in self.skipped:
+            _handler(self.HANDLERS, node)(self, node, ni)
+
+
+def run_forward(plan: Plan, x: torch.Tensor, packed: PackedWeights, keep: bool, training: bool = True,
+                deferred: Optional[Dict[int, torch.Tensor]] = None) -> Tuple[torch.Tensor, Optional[ForwardCtx]]:
+    """Execute `plan` on x (N,D,H,W,C).  keep=True records what backward needs.  training=True: batch-statistics BN (the
+    pretext step never runs anything else: pretrain.py:225); training=False: running-statistics BN for the fine-tune /
+    validation forward (finetune.py:333-345) and for fine-tuning with frozen BatchNorm (keep=True: the backward then runs
+    bn_eval_act_pool_bwd per ConvBN; no virtual stem, no grouped convolutions, no gate fusion in this mode, so Gate and Pool nodes
+    keep their ordinary saved state)."""
+    fw = _Forward(plan, x, packed, keep, training, deferred)
     branches = BranchStreams(x)
     for ni, node in enumerate(plan.nodes):
-        branches.run(node, lambda: run_node(ni, node))
+        branches.run(node, lambda: fw.run_node(ni, node))
     branches.finish()
-    out = slots[plan.output_slot]
+    out = fw.slots[plan.output_slot]
     if keep:
-        ctx.feat_shape = tuple(out.shape)
-    return out, ctx
+        fw.ctx.feat_shape = tuple(out.shape)
+    return out, fw.ctx
 
 
 def run_backward(plan: Plan, ctx: ForwardCtx, dfeat: torch.Tensor, grad_of, after_param_grads=None,
@@ -765,6 +784,179 @@ def run_backward(plan: Plan, ctx: ForwardCtx, dfeat: torch.Tensor, grad_of, afte
             next(it)
     except StopIteration as done:
         return done.value
+
+
+class _Backward:
+    """One backward through a plan: the state run_backward_iter's node handlers share, and one handler per node type; a ConvBN's
+    handler goes on by the type of record its forward saved."""
+
+    def __init__(self, plan, ctx, dfeat, grad_of, after_param_grads, want_input_grad, packed):
+        self.be = _ops.backend()
+        self.plan, self.ctx, self.grad_of, self.hook, self.want_input_grad = plan, ctx, grad_of, after_param_grads, want_input_grad
+        self.packed = packed if packed is not None else ctx.packed
+        self.dslots: Dict[int, torch.Tensor] = {plan.output_slot: dfeat}
+        self.branches = BranchStreams(dfeat)
+
+    def add_grad(self, slot, g):
+        # gradient accumulation at fan-out points; g is always the fresh output of the op that produced it, so the sum is
+        # written over it (no allocation, nothing else aliases it)
+        if g is None:
+            return
+        if slot in self.dslots:
+            self.dslots[slot] = self.be.eltwise("add", self.dslots[slot].contiguous(), g, out=g)
+        else:
+            self.dslots[slot] = g
+
+    def take_grad(self, node, C):
+        """The incoming gradient of a node's output: its channel slice of a concat tensor's gradient, or its own slot's (popped)."""
+        return _view(self.dslots[node.into[0]], node.into, C) if node.into is not None else self.dslots.pop(node.dst)
+
+    def issued(self, ni):
+        """The parameter gradients of node `ni` have been issued (see run_backward_iter: after_param_grads)."""
+        if self.hook is not None:
+            self.hook(ni, self.branches.grads_ready)
+
+    def input_grad(self, src, cg, dy, conv):
+        """dgrad into slot `src` — unless that is the plan's input and nobody asked for its gradient."""
+        if src != self.plan.input_slot or self.want_input_grad:
+            self.add_grad(src, self.be.conv_dgrad_packed(cg, dy, self.packed.get_dgrad(conv, cg)))
+
+    def convbn(self, node, ni, key=None):
+        key = ni if key is None else key
+        sv = self.ctx.saved.pop(key)
+        if isinstance(sv, _SavedVStem):
+            return self.convbn_virtual(node, sv, ni)
+        if sv.gate is not None:
+            return self.convbn_gated(node, sv, ni)
+        if sv.eval_mode:
+            return self.convbn_eval(node, sv, ni)
+        bn, grad_of = node.bn, self.grad_of
+        dout = self.take_grad(node, sv.cg.Cout)
+        dy, dres = self.be.bn_act_pool_bwd(sv.pg, sv.y, sv.res, dout, bn.weight.data, sv.mi, sv.ss, node.relu,
+                                           node.residual is not None, grad_of(bn.weight), grad_of(bn.bias))
+        self.convbn_tail(node, sv, ni, dy, dres, True)
+
+    def convbn_virtual(self, node, sv, ni):
+        be, grad_of, vs, cg = self.be, self.grad_of, sv.vs, sv.cg
+        assert node.src == self.plan.input_slot and not self.want_input_grad, "a virtual-pixel stem reads the clip: no input gradient"
+        dout = self.dslots.pop(node.dst)
+        bn = node.bn
+        dy, _ = be.bn_act_pool_bwd(sv.pg, sv.y, None, dout, bn.weight.data, sv.mi, sv.ss, node.relu, False, grad_of(bn.weight), grad_of(bn.bias))
+        gw = grad_of(node.conv.weight)
+        if gw is not None:
+            N, do, ho, Wo, Cp = dy.shape
+            dyv = dy.view(N, do, ho, Wo // 2, 2 * Cp)
+            gflat = gw.view(-1)
+            gflat.zero_()
+            for c, xc in enumerate((sv.x_e, sv.x_o)):
+                gv = torch.empty_like(vs.holders[c].weight)
+                be.conv_wgrad(cg, xc, dyv[..., c * Cp:(c + 1) * Cp], gv)
+                # every real filter element appears once in a class's virtual filter: unique indices, order-independent
+                gflat.index_add_(0, vs.dst[c], gv.view(-1).index_select(0, vs.src[c]))
+        self.issued(ni)
+
+    def convbn_gated(self, node, sv, ni):
+        """... with the self-gating unit behind this BatchNorm, whose forward kept no activation: both backwards as one op"""
+        bn, grad_of, sg = node.bn, self.grad_of, sv.gate
+        gnode = self.plan.nodes[sg.at]
+        dout = self.take_grad(gnode, sv.cg.Cout)
+        dy = self.be.bn_act_gate_bwd(sv.pg, sv.y, dout, bn.weight.data, sv.mi, sv.ss, node.relu, gnode.conv.weight.data, sg.mean, sg.gate,
+                                     grad_of(bn.weight), grad_of(bn.bias), grad_of(gnode.conv.weight), grad_of(gnode.conv.bias))
+        self.issued(sg.at)
+        self.convbn_tail(node, sv, ni, dy, None, True)
+
+    def convbn_eval(self, node, sv, ni):
+        """ConvBN whose forward ran BatchNorm on its running statistics: dy = scale * dz in one pass (bn_eval_act_pool_bwd)."""
+        be, grad_of = self.be, self.grad_of
+        if not hasattr(be, "bn_eval_act_pool_bwd"):
+            raise RuntimeError(EVAL_BACKWARD_MISSING)
+        bn = node.bn
+        dout = self.take_grad(node, sv.cg.Cout)
+        bias = getattr(node.conv, "bias", None)
+        gbias = grad_of(bias) if bias is not None else None
+        dgamma, dbeta = grad_of(bn.weight), grad_of(bn.bias)
+        # the bias gradient comes from the dbeta sums — also with frozen affine parameters: the sums then land in a scratch vector
+        sums = dbeta if (dbeta is not None or gbias is None) else torch.empty_like(bn.bias.data)
+        dy, dres = be.bn_eval_act_pool_bwd(sv.pg, sv.y, sv.res, dout, sv.mi, sv.ss, node.relu, node.residual is not None, dgamma, sums)
+        if gbias is not None:
+            # out = (conv + b) * scale + shift0: d/db = scale * sum dz.  (Train-mode BatchNorm subtracts the batch mean and cancels
+            # it; running statistics do not.)
+            torch.mul(sv.ss[0][:gbias.shape[0]], sums, out=gbias)
+        self.convbn_tail(node, sv, ni, dy, dres, False)
+
+    def convbn_tail(self, node, sv, ni, dy, dres, zero_bias):
+        """Behind the BatchNorm backward: residual fan-out, the weight gradient (beside the trunk where it is small), the hook, dgrad."""
+        be, grad_of = self.be, self.grad_of
+        if node.residual is not None:
+            self.add_grad(node.residual, dres)
+        bias = getattr(node.conv, "bias", None)
+        if bias is not None and zero_bias:
+            gb = grad_of(bias)
+            if gb is not None:
+                # A conv bias in front of train-mode BatchNorm has an identically-zero gradient (BN subtracts the
+                # batch mean); the reference's autograd produces ~1e-8 rounding noise there.
+                gb.zero_()
+        # (a channel-padded geometry writes only the parameter's own channels: the reduce drops the padding's gradients)
+        gw = grad_of(node.conv.weight)
+        # (side stream: a gradient hook — the bucketed all-reduce of the data-parallel path — joins the task before it lets a
+        #  bucket go, see run_backward_iter's docstring)
+        if (sv.cg.flops < BranchStreams.SMALL_WGRAD_FLOPS or
+                (sv.cg.flops < BranchStreams.MID_WGRAD_FLOPS and sv.cg.bytes < BranchStreams.MID_WGRAD_BYTES)):
+            self.branches.side_task(lambda: be.conv_wgrad(sv.cg, sv.x, dy, gw), (sv.x, dy), cost=float(sv.cg.flops))
+        else:
+            be.conv_wgrad(sv.cg, sv.x, dy, gw)
+        self.issued(ni)
+        self.input_grad(node.src, sv.cg, dy, node.conv)
+
+    def group(self, node, ni):
+        sv = self.ctx.saved.pop(ni, None)
+        ms = node.members
+        if sv is None:                                   # forward ran the members one by one
+            for j in range(len(ms) - 1, -1, -1):
+                self.convbn(ms[j], ni, (ni, j))
+            return
+        be, grad_of = self.be, self.grad_of
+        dy_cat = torch.empty_like(sv.y)
+        for m, p in zip(ms, sv.per):
+            be.bn_act_pool_bwd(p.pg, sv.y[..., p.off:p.off + p.C], None, self.take_grad(m, p.C), m.bn.weight.data, p.mi, p.ss, m.relu, False,
+                               grad_of(m.bn.weight), grad_of(m.bn.bias), dy_out=dy_cat[..., p.off:p.off + p.C])
+        gws = [grad_of(m.conv.weight) for m in ms]
+        gcat = _adjacent_cat(gws) if all(g is not None for g in gws) else None
+        if gcat is not None:
+            be.conv_wgrad(sv.cg, sv.x, dy_cat, gcat)
+        else:
+            tmp = torch.empty_like(node.cat.weight)
+            be.conv_wgrad(sv.cg, sv.x, dy_cat, tmp)
+            off = 0
+            for m, g in zip(ms, gws):
+                if g is not None:
+                    g.copy_(tmp[off:off + g.shape[0]])
+                off += m.conv.weight.shape[0]
+        self.issued(ni)
+        self.input_grad(ms[0].src, sv.cg, dy_cat, node.cat)
+
+    def convbias(self, node, ni):
+        sv = self.ctx.saved.pop(ni)
+        dout = self.dslots.pop(node.dst)
+        dz = self.be.eltwise("relu_bwd", sv.y, dout.contiguous()) if node.relu else dout.contiguous()
+        self.be.conv_wgrad(sv.cg, sv.x, dz, self.grad_of(node.conv.weight), self.grad_of(node.conv.bias))
+        self.issued(ni)
+        self.input_grad(node.src, sv.cg, dz, node.conv)
+
+    def pool(self, node, ni):
+        sv = self.ctx.saved.pop(ni)
+        self.add_grad(node.src, self.be.maxpool_bwd(sv.pg, self.dslots.pop(node.dst), sv.idx))
+
+    def gate(self, node, ni):
+        sv = self.ctx.saved.pop(ni)
+        if sv.x is None:      # its backward runs with the BatchNorm's in front of it (convbn_gated)
+            return
+        dout = self.take_grad(node, sv.x.shape[4])
+        self.add_grad(node.src, self.be.gate_bwd(sv.x, dout, node.conv.weight.data, sv.mean, sv.gate, self.grad_of(node.conv.weight),
+                                                 self.grad_of(node.conv.bias)))
+        self.issued(ni)
+
+    HANDLERS = {ConvBN: convbn, ConvBNGroup: group, ConvBias: convbias, Pool: pool, Gate: gate}
 
 
 def run_backward_iter(plan: Plan, ctx: ForwardCtx, dfeat: torch.Tensor, grad_of, after_param_grads=None,
@@ -780,176 +972,12 @@ def run_backward_iter(plan: Plan, ctx: ForwardCtx, dfeat: torch.Tensor, grad_of,
     stream context ordered behind all of them (BranchStreams.grads_ready).
     want_input_grad: also propagate to the plan's input slot and return that gradient (projection-head sub-plans, whose
     input is the backbone feature; the backbone's own input is the clip and needs none)."""
-    be = _ops.backend()
-    packed = packed if packed is not None else ctx.packed
-    dslots: Dict[int, torch.Tensor] = {plan.output_slot: dfeat}
-    branches = BranchStreams(dfeat)
-    fused_gates: Dict[int, Tuple] = {}      # key of a ConvBN -> (index, means, gates) of the gate fused behind it
-
-    def add_grad(slot, g):
-        # gradient accumulation at fan-out points; g is always the fresh output of the op that produced it, so the sum is
-        # written over it (no allocation, nothing else aliases it)
-        if g is None:
-            return
-        if slot in dslots:
-            dslots[slot] = be.eltwise("add", dslots[slot].contiguous(), g, out=g)
-        else:
-            dslots[slot] = g
-
-    def convbn_virtual_bwd(node, sv, ni):
-        _, x_e, x_o, y, mi, ss, cg, pg, vs = sv
-        assert node.src == plan.input_slot and not want_input_grad, "a virtual-pixel stem reads the clip: no input gradient"
-        dout = dslots.pop(node.dst)
-        bn = node.bn
-        dy, _ = be.bn_act_pool_bwd(pg, y, None, dout, bn.weight.data, mi, ss, node.relu, False, grad_of(bn.weight), grad_of(bn.bias))
-        gw = grad_of(node.conv.weight)
-        if gw is not None:
-            N, do, ho, Wo, Cp = dy.shape
-            dyv = dy.view(N, do, ho, Wo // 2, 2 * Cp)
-            gflat = gw.view(-1)
-            gflat.zero_()
-            for c, xc in enumerate((x_e, x_o)):
-                gv = torch.empty_like(vs.holders[c].conv.weight)
-                be.conv_wgrad(cg, xc, dyv[..., c * Cp:(c + 1) * Cp], gv)
-                # every real filter element appears once in a class's virtual filter: unique indices, order-independent
-                gflat.index_add_(0, vs.dst[c], gv.view(-1).index_select(0, vs.src[c]))
-        if after_param_grads is not None:
-            after_param_grads(ni, branches.grads_ready)
-
-    def convbn_bwd(node, key, ni):
-        sv = ctx.saved.pop(key)
-        if isinstance(sv, tuple) and sv[0] == "vstem":
-            return convbn_virtual_bwd(node, sv, ni)
-        bn = node.bn
-        gated = fused_gates.pop(key, None)
-        if gated is not None:
-            # the self-gating unit behind this BatchNorm, whose forward kept no activation: both backwards as one op
-            gi, mean, gate = gated
-            gnode = plan.nodes[gi]
-            dout = _view(dslots[gnode.into[0]], gnode.into, sv.cg.Cout) if gnode.into is not None else dslots.pop(gnode.dst)
-            dy = be.bn_act_gate_bwd(sv.pg, sv.y, dout, bn.weight.data, sv.mi, sv.ss, node.relu, gnode.conv.weight.data, mean, gate,
-                                    grad_of(bn.weight), grad_of(bn.bias), grad_of(gnode.conv.weight), grad_of(gnode.conv.bias))
-            dres = None
-            if after_param_grads is not None:
-                after_param_grads(gi, branches.grads_ready)
-        elif sv.eval_mode:
-            return convbn_eval_bwd(node, sv, ni)
-        else:
-            dout = _view(dslots[node.into[0]], node.into, sv.cg.Cout) if node.into is not None else dslots.pop(node.dst)
-            dy, dres = be.bn_act_pool_bwd(sv.pg, sv.y, sv.res, dout, bn.weight.data, sv.mi, sv.ss, node.relu,
-                                          node.residual is not None, grad_of(bn.weight), grad_of(bn.bias))
-        convbn_tail(node, sv, ni, dy, dres, True)
-
-    def convbn_eval_bwd(node, sv, ni):
-        """ConvBN whose forward ran BatchNorm on its running statistics: dy = scale * dz in one pass (bn_eval_act_pool_bwd)."""
-        if not hasattr(be, "bn_eval_act_pool_bwd"):
-            raise RuntimeError(EVAL_BACKWARD_MISSING)
-        bn = node.bn
-        dout = _view(dslots[node.into[0]], node.into, sv.cg.Cout) if node.into is not None else dslots.pop(node.dst)
-        bias = getattr(node.conv, "bias", None)
-        gbias = grad_of(bias) if bias is not None else None
-        dgamma, dbeta = grad_of(bn.weight), grad_of(bn.bias)
-        # the bias gradient comes from the dbeta sums — also with frozen affine parameters: the sums then land in a scratch vector
-        sums = dbeta if (dbeta is not None or gbias is None) else torch.empty_like(bn.bias.data)
-        dy, dres = be.bn_eval_act_pool_bwd(sv.pg, sv.y, sv.res, dout, sv.mi, sv.ss, node.relu, node.residual is not None, dgamma, sums)
-        if gbias is not None:
-            # out = (conv + b) * scale + shift0: d/db = scale * sum dz.  (Train-mode BatchNorm subtracts the batch mean and cancels
-            # it; running statistics do not.)
-            torch.mul(sv.ss[0][:gbias.shape[0]], sums, out=gbias)
-        convbn_tail(node, sv, ni, dy, dres, False)
-
-    def convbn_tail(node, sv, ni, dy, dres, zero_bias):
-        if node.residual is not None:
-            add_grad(node.residual, dres)
-        bias = getattr(node.conv, "bias", None)
-        if bias is not None and zero_bias:
-            gb = grad_of(bias)
-            if gb is not None:
-                # A conv bias in front of train-mode BatchNorm has an identically-zero gradient (BN subtracts the
-                # batch mean); the reference's autograd produces ~1e-8 rounding noise there.
-                gb.zero_()
-        # (a channel-padded geometry writes only the parameter's own channels: the reduce drops the padding's gradients)
-        gw = grad_of(node.conv.weight)
-        # (side stream: a gradient hook — the bucketed all-reduce of the data-parallel path — joins the task before it lets a
-        #  bucket go, see run_backward's docstring)
-        if (sv.cg.flops < BranchStreams.SMALL_WGRAD_FLOPS or
-                (sv.cg.flops < BranchStreams.MID_WGRAD_FLOPS and sv.cg.bytes < BranchStreams.MID_WGRAD_BYTES)):
-            branches.side_task(lambda: be.conv_wgrad(sv.cg, sv.x, dy, gw), (sv.x, dy), cost=float(sv.cg.flops))
-        else:
-            be.conv_wgrad(sv.cg, sv.x, dy, gw)
-        if after_param_grads is not None:
-            after_param_grads(ni, branches.grads_ready)
-        if node.src != plan.input_slot or want_input_grad:
-            add_grad(node.src, be.conv_dgrad_packed(sv.cg, dy, packed.get_dgrad(node, sv.cg)))
-
-    def convbn_group_bwd(node, ni):
-        sv = ctx.saved.pop(ni, None)
-        ms = node.members
-        if sv is None:                                   # forward ran the members one by one
-            for j in range(len(ms) - 1, -1, -1):
-                convbn_bwd(ms[j], (ni, j), ni)
-            return
-        _, xin, y, cg, per = sv
-        dy_cat = torch.empty_like(y)
-        for m, (off, C, mi, ss, pg) in zip(ms, per):
-            dout = _view(dslots[m.into[0]], m.into, C) if m.into is not None else dslots.pop(m.dst)
-            be.bn_act_pool_bwd(pg, y[..., off:off + C], None, dout, m.bn.weight.data, mi, ss, m.relu, False,
-                               grad_of(m.bn.weight), grad_of(m.bn.bias), dy_out=dy_cat[..., off:off + C])
-        gws = [grad_of(m.conv.weight) for m in ms]
-        gcat = _adjacent_cat(gws) if all(g is not None for g in gws) else None
-        if gcat is not None:
-            be.conv_wgrad(cg, xin, dy_cat, gcat)
-        else:
-            tmp = torch.empty_like(node._cat.weight)
-            be.conv_wgrad(cg, xin, dy_cat, tmp)
-            off = 0
-            for m, g in zip(ms, gws):
-                if g is not None:
-                    g.copy_(tmp[off:off + g.shape[0]])
-                off += m.conv.weight.shape[0]
-        if after_param_grads is not None:
-            after_param_grads(ni, branches.grads_ready)
-        if ms[0].src != plan.input_slot or want_input_grad:
-            add_grad(ms[0].src, be.conv_dgrad_packed(cg, dy_cat, packed.get_dgrad(node._cat_node(), cg)))
-
-    def run_node(ni, node):
-        if isinstance(node, ConvBN):
-            convbn_bwd(node, ni, ni)
-        elif isinstance(node, ConvBNGroup):
-            convbn_group_bwd(node, ni)
-        elif isinstance(node, ConvBias):
-            xin, y, cg = ctx.saved.pop(ni)
-            dout = dslots.pop(node.dst)
-            dz = be.eltwise("relu_bwd", y, dout.contiguous()) if node.relu else dout.contiguous()
-            be.conv_wgrad(cg, xin, dz, grad_of(node.conv.weight), grad_of(node.conv.bias))
-            if after_param_grads is not None:
-                after_param_grads(ni, branches.grads_ready)
-            if node.src != plan.input_slot or want_input_grad:
-                add_grad(node.src, be.conv_dgrad_packed(cg, dz, packed.get_dgrad(node, cg)))
-            del dz, dout
-        elif isinstance(node, Pool):
-            pg, idx = ctx.saved.pop(ni)
-            add_grad(node.src, be.maxpool_bwd(pg, dslots.pop(node.dst), idx))
-        elif isinstance(node, Gate):
-            sv = ctx.saved.pop(ni)
-            if sv[0] == "fused":      # its backward runs with the BatchNorm's in front of it (convbn_bwd)
-                fused_gates[sv[1]] = (ni, sv[2], sv[3])
-                return
-            xin, mean, gate = sv
-            dout = (_view(dslots[node.into[0]], node.into, xin.shape[4]) if node.into is not None
-                    else dslots.pop(node.dst))
-            add_grad(node.src, be.gate_bwd(xin, dout, node.conv.weight.data, mean, gate, grad_of(node.conv.weight),
-                                           grad_of(node.conv.bias)))
-            if after_param_grads is not None:
-                after_param_grads(ni, branches.grads_ready)
-        else:
-            raise NotImplementedError(f"plan node {type(node).__name__}")
-
+    bw = _Backward(plan, ctx, dfeat, grad_of, after_param_grads, want_input_grad, packed)
     # (side branches of a block — engine.BranchStreams — each own their slots; the fan-out sum at the block's input happens on the
     #  trunk after the join: the block's last backward node, the grouped pointwise convolution, is a trunk node)
     for ni in range(len(plan.nodes) - 1, -1, -1):
         node = plan.nodes[ni]
-        branches.run(node, lambda: run_node(ni, node))
+        bw.branches.run(node, lambda: _handler(bw.HANDLERS, node)(bw, node, ni))
         yield ni
-    branches.finish()
-    return dslots.get(plan.input_slot) if want_input_grad else None
+    bw.branches.finish()
+    return bw.dslots.get(plan.input_slot) if want_input_grad else None

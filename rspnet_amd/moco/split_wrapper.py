@@ -255,7 +255,7 @@ class _FinetuneFn(torch.autograd.Function):
         training = module.encoder.training                 # BatchNorm mode (only_train_fc / freeze_bn keep the backbone in eval mode)
         names = [n for n, _ in module.named_parameters()]
         backbone_grad = grad_on and any(need for n, need in zip(names, ctx.needs_input_grad[3:]) if n.startswith("encoder."))
-        keep = backbone_grad                               # eval mode too: frozen BatchNorm (engine.convbn_eval_bwd)
+        keep = backbone_grad                               # eval mode too: frozen BatchNorm (engine._Backward.convbn_eval)
         ctx.backbone_grad = backbone_grad
         ctx.bn_training = training
         # weights may have been stepped by any optimizer since the last call: re-pack when their version counters moved

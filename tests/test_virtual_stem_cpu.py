@@ -25,7 +25,7 @@ def test_virtual_filters_hold_every_weight_once():
     node = engine.ConvBN(conv, nn.BatchNorm3d(5), 0, 1, (3, 7, 7), (1, 2, 2), (1, 3, 3), virtual_w=True)
     vs = engine.VirtualStem(node)
     for c in range(2):
-        hv = vs.holders[c].conv.weight.view(-1)
+        hv = vs.holders[c].weight.view(-1)
         assert sorted(vs.dst[c].tolist()) == list(range(conv.weight.numel()))
         assert torch.equal(hv[vs.src[c]], conv.weight.data.view(-1)[vs.dst[c]])
         mask = torch.ones_like(hv, dtype=torch.bool)
