@@ -531,6 +531,48 @@ int rsp_cam_maps(const float* feat_q, int32_t ld_q, const float* feat_k, int32_t
 int rsp_cam_overlay(const float* maps, int32_t N, int32_t Tp, int32_t Hp, int32_t Wp, const float* clip_a, const float* clip_b,
                     int32_t B, int32_t T, int32_t t, int32_t size, uint8_t* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Step fingerprints (fingerprint.hip; the project's own, no counterpart in the reference): one 32-byte record per tensor of a list
+ * of device tensors, from one call.  Additive: the ABI version stays 130.
+ *
+ * jobs_dev: DEVICE table of n_jobs entries.
+ *   ptr      the tensor's first word, 4-byte aligned (16-byte alignment is used when present and changes no result);
+ *   words    its length in 32-bit words, 0 <= words < 2^31 (0: an all-zero record);
+ *   chunk0   running sum of ceil(words / RSP_FP_CHUNK) over the preceding jobs; total_chunks is the sum over all jobs (<= 2^23);
+ *   kind     0: fp32 data; 1: raw words (an int64 tensor passes 2 * numel): only `hash` is formed, the other fields are 0.
+ * out_dev: n_jobs records.  With w_i the i-th word as uint32, i from 0, v_i the same word as fp32:
+ *   hash       sum_i fmix32((w_i + i * 0x9E3779B1) mod 2^32) mod 2^64, fmix32 = murmur3's 32-bit finaliser (x ^= x >> 16;
+ *              x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16).  A bijection per word: a change of any single word
+ *              always changes the hash; several simultaneous changes escape with probability about 2^-32 per tensor.  Position
+ *              dependent: a swap of two unequal elements is seen.
+ *   nonfinite  number of words whose exponent field is all ones; those stay in the hash and are left out of the next three.
+ *   sumsq, sum_abs   fp64 sums of v_i^2 (exact squares) and |v_i|;   max_abs   exact fp32 maximum of |v_i| (0 if none).
+ * The record is a function of the values only: the same words at another address or alignment, on another stream or in another
+ * process give the same 32 bytes, the doubles included (the summation order depends on `words` alone).
+ * workspace: rsp_fingerprint_workspace(total_chunks) bytes (32 per chunk), 8-byte aligned; may be NULL when total_chunks is 0.
+ * n_jobs == 0 returns 0 without a launch.  A negative count, a null or misaligned pointer or a bad total_chunks is RSP_EINVAL, a
+ * workspace below the query RSP_EWORKSPACE, both before anything is launched.  Two kernel launches, no memset / memcpy, no
+ * atomics: capturable.  The table itself is not checked (it is on the device): a chunk it does not describe contributes zeros.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define RSP_FP_CHUNK 8192 /* 32-bit words per partial */
+typedef struct rsp_fingerprint_job {
+  const void* ptr;
+  int64_t words;
+  int64_t chunk0;
+  int32_t kind;
+  int32_t reserved;
+} rsp_fingerprint_job; /* 32 bytes */
+typedef struct rsp_fingerprint_rec {
+  uint64_t hash;
+  double sumsq;
+  double sum_abs;
+  float max_abs;
+  uint32_t nonfinite;
+} rsp_fingerprint_rec; /* 32 bytes */
+size_t rsp_fingerprint_workspace(int64_t total_chunks);
+int rsp_fingerprint(const rsp_fingerprint_job* jobs_dev, int32_t n_jobs, int64_t total_chunks, rsp_fingerprint_rec* out_dev,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,17 @@ class PretextMeters(C.Structure):
     _fields_ = [("val", C.c_float * 8), ("sum", C.c_float * 8), ("count", C.c_int32 * 8)]
 
 
+class FingerprintJob(C.Structure):
+    """rsp_fingerprint_job (32 bytes)"""
+    _fields_ = [("ptr", C.c_void_p), ("words", C.c_int64), ("chunk0", C.c_int64), ("kind", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FingerprintRec(C.Structure):
+    """rsp_fingerprint_rec (32 bytes)"""
+    _fields_ = [("hash", C.c_uint64), ("sumsq", C.c_double), ("sum_abs", C.c_double), ("max_abs", C.c_float),
+                ("nonfinite", C.c_uint32)]
+
+
 _PD = C.POINTER(ConvDesc)
 _PP = C.POINTER(PoolDesc)
 _sz = C.c_size_t
@@ -152,6 +163,8 @@ SIGNATURES = {
     "rsp_cam_maps_workspace": (_sz, [_i32, _i32]),
     "rsp_cam_maps": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _sz, _p]),
     "rsp_cam_overlay": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "rsp_fingerprint_workspace": (_sz, [_i64]),
+    "rsp_fingerprint": (C.c_int, [_p, _i32, _i64, _p, _p, _sz, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -23,7 +23,7 @@ import torch
 import torch.distributed as dist
 from torch import Tensor, nn
 
-from . import _lib, ops
+from . import _lib, fingerprint, ops
 from .framework.arguments import add_driver_arguments, parse_driver_args
 from .framework.driver import (append_scalars, finish_process_group, init_process_group, launch, load_config, load_states, save_run,
                                seed_everything, setup_logging)
@@ -304,6 +304,8 @@ class Engine:
         self.checkpoint_manager = CheckpointManager(args.experiment_dir, keep_interval=None)
         run_dir = getattr(args, "run_dir", None)
         self.scalars_path = None if run_dir is None or local_rank != 0 else Path(run_dir) / "scalars.jsonl"
+        # opt-in (config key "fingerprint", e.g. -x '{"fingerprint": {"every": 50, "halt_on_nonfinite": true}}'): None otherwise
+        self.fingerprints = fingerprint.StepFingerprints.from_config(cfg, run_dir, rank=local_rank)
 
     def _synthetic(self, split: str):
         cfg, a = self.cfg, self.args
@@ -354,9 +356,15 @@ class Engine:
                 logger.info(f"{name} [{self.current_epoch}/{self.num_epochs}][{i - 1}/{num_iters}]\t" + "\t".join(meters.pieces()))
             loss = self.criterion(output, target, n_crop=n_crop, valid=batch_size, meters=meters)
             if train:
+                fp = self.fingerprints
+                due = fp is not None and fp.due(self.current_epoch * num_iters + i)
                 self.optimizer.zero_grad()
                 loss.backward()
+                if due:
+                    fp.after_backward(self.model)      # (halt_on_nonfinite raises here: the parameters stay as they were)
                 self.optimizer.step()
+                if due:
+                    fp.after_step(self.current_epoch, i, self.model)
         stats = meters.read()
         logger.info("%s epoch finished. Time: %.2f sec.\t%s\t%s\t%s", name, time.perf_counter() - begin_time, *meters.pieces(stats))
         return meters, stats

@@ -809,6 +809,23 @@ class HipOps:
                                                 _ptr(meters_buf), _ptr(ws), wsb, _stream()), "rsp_pretext_metrics")
         return acc
 
+    # ---- step fingerprints (fingerprint.hip) ---------------------------------------------------------------------------
+    def fingerprint(self, table, n_jobs: int, total_chunks: int, out):
+        """One 32-byte record per job of a device-resident rsp_fingerprint_job table (rsp_fingerprint; rspnet_amd/fingerprint.py
+        builds the table and reads the records).  table: uint8, n_jobs * 32 bytes; out: uint8, n_jobs * 32 bytes, every record written."""
+        _chk(table, "table", torch.uint8)
+        _chk(out, "out", torch.uint8)
+        n_jobs, total_chunks = int(n_jobs), int(total_chunks)
+        rec = C.sizeof(_lib.FingerprintRec)
+        if n_jobs < 0 or table.numel() < n_jobs * C.sizeof(_lib.FingerprintJob) or out.numel() < n_jobs * rec:
+            raise _lib.RspError(f"fingerprint: {n_jobs} jobs do not fit a table of {table.numel()} and records of {out.numel()} bytes")
+        if total_chunks < 0 or table.device != out.device:
+            raise _lib.RspError("fingerprint: total_chunks must not be negative, table and records on one device")
+        wsb = int(self.lib.rsp_fingerprint_workspace(total_chunks))
+        ws = self._workspace(out.device, wsb)
+        _lib.check(self.lib.rsp_fingerprint(_ptr(table), n_jobs, total_chunks, _ptr(out), _ptr(ws), wsb, _stream()), "rsp_fingerprint")
+        return out
+
     # ---- similarity maps and their picture panels (cam.hip) --------------------------------------------------------
     def cam_maps(self, feat_q, feat_k, k_row, w_qA, w_qM, w_kA, w_kM):
         """The four similarity maps of MoCoDiffLossTwoFc.cam_visualize from the two NDHWC feature maps (B, T', H', W', C) — dense, or

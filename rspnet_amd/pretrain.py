@@ -22,7 +22,7 @@ from pathlib import Path
 
 import torch
 
-from . import _lib, ops
+from . import _lib, fingerprint, ops
 from .framework.arguments import RUN_DIR_NAME_REGEX, add_driver_arguments, parse_driver_args, save_run_files  # noqa: F401
 from .framework.driver import (append_scalars, finish_process_group, init_process_group, launch, load_config, load_states, save_run,
                                seed_everything, setup_logging, visible_gpu_count)
@@ -167,6 +167,8 @@ class Engine:
         self.meters, self.stats = None, None
         run_dir = getattr(args, "run_dir", None)
         self.scalars_path = None if run_dir is None or local_rank != 0 else Path(run_dir) / "scalars.jsonl"
+        # opt-in (config key "fingerprint", e.g. -x '{"fingerprint": {"every": 50, "halt_on_nonfinite": true}}'): None otherwise
+        self.fingerprints = fingerprint.StepFingerprints.from_config(cfg, run_dir, rank=local_rank)
         T, size = int(cfg["temporal_transforms"]["size"]), int(cfg["spatial_transforms"]["size"])
         if train_loader is None and getattr(args, "loader", "tensor") == "uint8":
             train_loader = SyntheticVideoClips(self.batch_size, T, size, args.steps_per_epoch, self.device,
@@ -238,6 +240,13 @@ class Engine:
                             f"\t{p[1]}\t{p[2]}\t{p[3]}\n{p[6]}\t{p[7]}\n{p[4]}\t{p[5]}")
             # the stepper's tensors are the graphs' output buffers: consumed here, before the next step overwrites them
             self._update_meters(loss, loss_A, loss_M, output, ranking_logits)
+            fp = self.fingerprints
+            if fp is not None and fp.due(self.current_epoch * num_iters + it):
+                # behind the step, eagerly on its stream (never captured): the gradients are still in g_flat, the state is as updated.
+                # --validate: state only.  A halt leaves this epoch's checkpoint unwritten.
+                if not validate:
+                    fp.after_backward(self.model)
+                fp.after_step(self.current_epoch, it, self.model)
             n += 1
         torch.cuda.synchronize(self.device)
         dt = time.perf_counter() - t0

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from golden_util import load_spec  # noqa: E402
 from model_util import make_cfg  # noqa: E402
 from oracle import portable as P  # noqa: E402  (test infrastructure: seeded states and clips only)
+from rspnet_amd import fingerprint as F  # noqa: E402
 
 
 def main():
@@ -40,7 +41,7 @@ def main():
         crit = Loss(margin=2.0, A=1.0, M=1.0)
         opt = SGD(wrapped.parameters(), lr=0.05, momentum=0.9, dampening=0.0, weight_decay=1e-4, nesterov=False)
         stepper = GraphedPretextStep(wrapped, crit, opt, warmup=2, issue="graph") if how == "graph" else None
-        trace = []
+        trace, fsets = [], None
         for i in range(steps):
             im_q, im_k = clips[i % len(clips)]
             if stepper is None:
@@ -53,15 +54,16 @@ def main():
                 loss, la, lm, out, rl = stepper(im_q, im_k)
             sd = wrapped.module.state_dict()
             if light:
-                fl = wrapped.module._flat
-                per = torch.stack([fl.g_flat[o:o + n].double().abs().sum() for o, n in (fl.offsets[nm] for nm in fl.names[:fl.n_trained_params])])
-                bns = torch.stack([b.double().sum() for k, b in sd.items() if k.endswith(("running_mean", "running_var"))])
-                trace.append((loss.detach().clone(), out[0].detach().clone(), fl.g_flat.double().sum().reshape(1),
-                              {"q_flat": fl.q_flat.double().sum().reshape(1), "k_flat": fl.k_flat.double().sum().reshape(1),
-                               "bn": wrapped.module._bn_flat.double().sum().reshape(1), "queue": wrapped.module.queue.double().sum().reshape(1),
-                               "per_param_grad": per, "per_bn_buffer": bns}))
-                pnames = list(fl.names[:fl.n_trained_params])
-                bnames = [k for k in sd if k.endswith(("running_mean", "running_var"))]
+                # one fingerprint call each for the gradients and the state (rspnet_amd/fingerprint.py): exact bit hashes per tensor,
+                # kept on the device until the comparison
+                if fsets is None:
+                    fl = wrapped.module._flat
+                    pnames = list(fl.names[:fl.n_trained_params])
+                    fsets = (F.FingerprintSet(pnames, [fl.g_flat[o:o + n] for o, n in (fl.offsets[nm] for nm in pnames)]),
+                             F.FingerprintSet(*zip(*F.named_state(wrapped))))
+                    snames = fsets[1].names
+                trace.append((loss.detach().clone(), out[0].detach().clone(), fsets[0].run(),
+                              {"state": fsets[1].run([sd[k] for k in snames])}))
             else:
                 trace.append((loss.detach().clone(), out[0].detach().clone(), wrapped.module._flat.g_flat.clone(),
                               {k: v.detach().clone() for k, v in sd.items() if k.startswith("encoder_q")}))
@@ -75,14 +77,15 @@ def main():
         first = {}
         for tag, a, b in (("eager vs graph", te, tg), ("graph vs graph (second run)", tg, tg2)):
             for i, ((l0, o0, g0, s0), (l1, o1, g1, s1)) in enumerate(zip(a, b)):
-                bad = [n for n, x, y in (("loss", l0, l1), ("logits", o0, o1), ("grad checksum", g0, g1)) if not torch.equal(x, y)]
+                bad = [n for n, x, y in (("loss", l0, l1), ("logits", o0, o1), ("grad fingerprints", g0, g1)) if not torch.equal(x, y)]
                 bad += [k for k in s0 if not torch.equal(s0[k], s1[k])]
                 if bad:
                     first[tag] = (i, bad, float(l0), float(l1))
-                    dp = (s0["per_param_grad"] != s1["per_param_grad"]).nonzero().flatten().tolist()
-                    db = (s0["per_bn_buffer"] != s1["per_bn_buffer"]).nonzero().flatten().tolist()
+                    dp = (g0 != g1).any(dim=1).nonzero().flatten().tolist()
+                    ds = (s0["state"] != s1["state"]).any(dim=1).nonzero().flatten().tolist()
                     print(tag, "step", i, ":", len(dp), "of", len(pnames), "parameter gradients differ:", [pnames[j] for j in dp][:12],
-                          "...", [pnames[j] for j in dp][-4:], ";", len(db), "BN buffers differ:", [bnames[j] for j in db][:8])
+                          "...", [pnames[j] for j in dp][-4:], ";", len(ds), "of", len(snames), "state tensors differ:",
+                          [snames[j] for j in ds][:8])
                     break
             print(tag, "-> first difference:", first.get(tag, "none in %d steps" % len(a)))
         print("final losses", float(te[-1][0]), float(tg[-1][0]), float(tg2[-1][0]))
