@@ -445,6 +445,35 @@ int rsp_topk_hits(const int32_t* idx, int32_t Nq, int32_t k, const int64_t* y_q,
                   const int32_t* ks_host, int32_t nks, int32_t* counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Weighted kNN classifier (knn.hip): the monitor of a pretext run -- the k nearest labelled gallery rows of every query vote for
+ * their class with weight exp(s / T); top-1 / top-5 hits of the queries' own labels.  One call, the Nq x Ng matrix never stored.
+ * q, g, ldq, ldg, D, splits: as for the search above (D and the pitches even, ld >= D, 8-byte aligned bases).  1 <= k <= 256,
+ * 1 <= num_classes <= 1024, T finite and >= 0.01.  y_g: Ng int64 labels; y_q: Nq int64 labels or NULL.
+ *   neighbours  the search's rule: s = (q.g) * (1/|q|) * (1/|g|) in fp32 (a zero-norm row: inverse norm 0), s descending, an exact
+ *               tie to the lower gallery index, independent of `splits`; a NaN similarity never enters a list.  Ng < k: only Ng
+ *               neighbours exist and vote.
+ *   idx, dist   [Nq][k], both or neither (may be NULL): as the search writes them (-1 / +inf past Ng); for k <= 64 the search's
+ *               output bit for bit.
+ *   weights     w_j = expf((s_j - 1) * (1/T)), 1/T formed once on the host as a float: every class of a query is scaled by the
+ *               same exp(-1/T), so the ranking is that of exp(s / T) and nothing overflows.
+ *   votes       [Nq][num_classes] (may be NULL): votes[i][c] = sum of w_j over the neighbours j of query i with y_g[j] == c, in
+ *               fp32 in neighbour-rank order, rank 0 first.  No floating-point atomics: the bits depend on the values only.  A
+ *               gallery label outside [0, num_classes) casts no vote.
+ *   pred        [Nq]: the class with the largest vote, an exact tie to the lower class index.
+ *   rank        [Nq], required if and only if y_q is given: #{c : v[c] > v[t]} + #{c < t : v[c] == v[t]}, t = y_q[i] (the tie rule
+ *               of rsp_xent_metrics); num_classes -- a miss -- for a y_q[i] outside [0, num_classes).
+ *   hits        [2] (may be NULL; needs y_q): the number of i < valid with rank[i] < 1 and with rank[i] < 5 (also written when
+ *               num_classes < 5).  0 <= valid <= Nq cuts the repeated tail of a wrapped last batch.
+ * A bad argument is RSP_EINVAL, a workspace below rsp_knn_classify_workspace RSP_EWORKSPACE, before anything is launched.
+ * Kernels only, all on `stream`.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t rsp_knn_classify_workspace(int32_t Nq, int32_t Ng, int32_t D, int32_t k, int32_t num_classes, int32_t splits);
+int rsp_knn_classify(const float* q, int32_t ldq, int32_t Nq, const int64_t* y_q, const float* g, int32_t ldg, int32_t Ng,
+                     const int64_t* y_g, int32_t D, int32_t k, float T, int32_t num_classes, int32_t splits, int32_t valid,
+                     int32_t* idx, float* dist, float* votes, int32_t* pred, int32_t* rank, int32_t* hits, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Everything behind the classifier's logits in the fine-tune loop (classify.hip; the reference's finetune.py:101-143), one call:
  * EpochContext.average_logits (:54-61), nn.CrossEntropyLoss forward + gradient (:105, Engine.criterion :187), the tail cut
  * (:112-119), accuracy(output, target, topk=(1, 5)) (:132-139, framework/metrics/classification.py:6-20) and the three

@@ -156,6 +156,9 @@ SIGNATURES = {
     "rsp_cosine_topk_workspace": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "rsp_cosine_topk": (C.c_int, [_p, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _sz, _p]),
     "rsp_topk_hits": (C.c_int, [_p, _i32, _i32, _p, _p, _i32, C.POINTER(C.c_int32), _i32, _p, _p]),
+    "rsp_knn_classify_workspace": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "rsp_knn_classify": (C.c_int, [_p, _i32, _i32, _p, _p, _i32, _i32, _p, _i32, _i32, _f, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p,
+                                   _p, _sz, _p]),
     "rsp_xent_metrics_workspace": (_sz, [_i32, _i32]),
     "rsp_xent_metrics": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "rsp_pretext_metrics_workspace": (_sz, [_i32]),

@@ -182,6 +182,12 @@ class MultiTaskWrapper(nn.Module):
             ctx.head = saved
         return outs[0], outs[1], ctx
 
+    def features_ndhwc(self, x: Tensor, training: bool = False) -> Tensor:
+        """x: (N,T,H,W,C).  The backbone's NDHWC feature map alone: its plan with nothing kept for a backward; the heads do not run
+        and `self.feat` stays what the last forward left (rspnet_amd.knn.extract: eval-mode features between training steps)."""
+        feat, _ = run_forward(self.plan(), x, self._packed, False, training=training)
+        return feat
+
     def backward_ndhwc(self, ctx, d1: Tensor, d2: Tensor, grad_of, after_param_grads=None):
         for _ in self.backward_ndhwc_iter(ctx, d1, d2, grad_of, after_param_grads):
             pass

@@ -181,6 +181,9 @@ def _dy_target(y, in_ld: int, dy_out):
     return torch.empty_like(y)
 
 
+KnnResult = collections.namedtuple("KnnResult", "pred rank hits votes idx dist")      # of HipOps.knn_classify
+
+
 class HipOps:
     """Calls into librspnet_hip.so on the current HIP stream of the current device."""
 
@@ -751,6 +754,47 @@ class HipOps:
         _lib.check(self.lib.rsp_topk_hits(_ptr(idx), idx.shape[0], idx.shape[1], _ptr(y_q), _ptr(y_g), y_g.shape[0], ks_host,
                                           len(ks), _ptr(counts), _stream()), "rsp_topk_hits")
         return counts
+
+    # ---- weighted kNN classifier (knn.hip) -------------------------------------------------------------------------
+    def knn_classify(self, q, g, y_g, k: int, T: float, num_classes: int, y_q=None, valid: Optional[int] = None, splits: int = 0,
+                     want_idx: bool = False, want_votes: bool = False):
+        """The k (1..256) cosine neighbours in g (Ng, D) of every row of q (Nq, D) vote for their class y_g with weight
+        exp((s - 1) / T) (rsp_knn_classify; the search's ranking and tie rules, the Nq x Ng matrix never stored).  Returns the named
+        tuple (pred int32 (Nq,), rank int32 (Nq,) | None, hits int32 (2,) | None, votes fp32 (Nq, num_classes) | None, idx int32
+        (Nq, k) | None, dist fp32 (Nq, k) | None).  rank -- #classes that beat the query's own, ties to the lower class -- and hits
+        -- rows i < valid with rank < 1 and rank < 5 -- come with y_q; votes / idx and dist when asked for.  Rows of q and g may be
+        strided (unit column stride, even row pitch)."""
+        for n, t in (("q", q), ("g", g)):
+            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+                raise _lib.RspError(f"knn_classify: {n} must be a float32 HIP device matrix with unit column stride")
+        Nq, D = q.shape
+        Ng = g.shape[0]
+        if g.shape[1] != D:
+            raise _lib.RspError(f"knn_classify: feature dims differ ({D} vs {g.shape[1]})")
+        _chk(y_g, "y_g", torch.int64)
+        if y_g.numel() != Ng:
+            raise _lib.RspError(f"knn_classify: {Ng} gallery rows, {y_g.numel()} labels")
+        if y_q is not None:
+            _chk(y_q, "y_q", torch.int64)
+            if y_q.numel() != Nq:
+                raise _lib.RspError(f"knn_classify: {Nq} query rows, {y_q.numel()} labels")
+        elif valid is not None:
+            raise _lib.RspError("knn_classify: valid counts hits, which need y_q")
+        k, num_classes, dev = int(k), int(num_classes), q.device
+        shaped = 1 <= k <= 256 and 1 <= num_classes <= 1024          # (the call itself rejects the rest, before any launch)
+        pred = torch.empty(Nq, dtype=torch.int32, device=dev)
+        rank = torch.empty(Nq, dtype=torch.int32, device=dev) if y_q is not None else None
+        hits = torch.empty(2, dtype=torch.int32, device=dev) if y_q is not None else None
+        votes = torch.empty((Nq, num_classes), dtype=torch.float32, device=dev) if want_votes and shaped else None
+        idx = torch.empty((Nq, k), dtype=torch.int32, device=dev) if want_idx and shaped else None
+        dist = torch.empty((Nq, k), dtype=torch.float32, device=dev) if want_idx and shaped else None
+        wsb = int(self.lib.rsp_knn_classify_workspace(Nq, Ng, D, k, num_classes, int(splits))) if shaped else 0
+        ws = self._workspace(dev, wsb)
+        _lib.check(self.lib.rsp_knn_classify(_ptr(q), q.stride(0) if Nq > 1 else D, Nq, _ptr(y_q), _ptr(g), g.stride(0) if Ng > 1 else D,
+                                             Ng, _ptr(y_g), D, k, float(T), num_classes, int(splits), Nq if valid is None else int(valid),
+                                             _ptr(idx), _ptr(dist), _ptr(votes), _ptr(pred), _ptr(rank), _ptr(hits), _ptr(ws), wsb,
+                                             _stream()), "rsp_knn_classify")
+        return KnnResult(pred, rank, hits, votes, idx, dist)
 
     # ---- fine-tune criterion, accuracy and meters (classify.hip) -------------------------------------------------
     def xent_metrics(self, logits, target, n_crop: int = 1, valid: Optional[int] = None, want_grad: bool = True, meters=None):

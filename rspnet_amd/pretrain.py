@@ -22,7 +22,7 @@ from pathlib import Path
 
 import torch
 
-from . import _lib, fingerprint, ops
+from . import _lib, fingerprint, knn, ops
 from .framework.arguments import RUN_DIR_NAME_REGEX, add_driver_arguments, parse_driver_args, save_run_files  # noqa: F401
 from .framework.driver import (append_scalars, finish_process_group, init_process_group, launch, load_config, load_states, save_run,
                                seed_everything, setup_logging, visible_gpu_count)
@@ -139,7 +139,7 @@ class SyntheticVideoClips:
 
 
 class Engine:
-    def __init__(self, args, cfg: dict, local_rank: int, train_loader=None):
+    def __init__(self, args, cfg: dict, local_rank: int, train_loader=None, knn_loaders=None):
         self.args, self.cfg, self.local_rank = args, cfg, local_rank
         self._stepper, self._first_epoch = None, 0
         self.device = torch.device("cuda", local_rank)
@@ -175,6 +175,12 @@ class Engine:
                                                seed=args.seed + local_rank, aug_plus=bool(cfg.get("moco", {}).get("aug_plus", False)))
         self.train_loader = train_loader or SyntheticClips(self.batch_size, T, size, args.steps_per_epoch, self.device,
                                                            seed=args.seed + local_rank)
+        # opt-in (config key "knn_monitor", e.g. -x '{"knn_monitor": {"every": 10, "num_classes": 101}}'): None otherwise.  Rank 0
+        # classifies; knn_loaders: a (bank, query) pair yielding ((clip,), target), the synthetic labelled clips by default
+        self.knn = knn.KNNMonitor.from_config(cfg, self.num_epochs)
+        self.knn_loaders, self._knn_result = knn_loaders, None
+        if self.knn is not None and knn_loaders is None and local_rank == 0:
+            self.knn_loaders = self.knn.build_loaders(T, size, self.device, seed=args.seed)
 
     # ---- checkpoints (pretrain.py:112-132) ---------------------------------------------------------------------------
     def load_checkpoint(self, path):
@@ -259,7 +265,23 @@ class Engine:
         """One line per epoch in RUN_DIR/scalars.jsonl (rank 0): what pretrain.py:199-218,240 hands to the summary writer."""
         rec = {"epoch": self.current_epoch, "train/lr": lr}
         rec.update({f"train/{k}": self.stats[k]["avg"] for k in ("loss", "loss_A", "acc1_A", "acc5_A", "loss_M", "acc1_M")})
+        if self._knn_result is not None:
+            rec.update({"knn/acc1": self._knn_result["acc1"], "knn/acc5": self._knn_result["acc5"]})
         append_scalars(self.scalars_path, rec)
+
+    def _run_knn_monitor(self):
+        """After the epoch's last step (train_epoch has waited for it) and before its scalar line: rank 0 classifies eagerly, in eval
+        mode, on the current stream; the other ranks wait at a barrier.  Has run on one GPU only."""
+        self._knn_result = None
+        m = self.knn
+        if m is None or not m.due(self.current_epoch):
+            return
+        if self.local_rank == 0:
+            r = self._knn_result = m.run(self.model, *self.knn_loaders)
+            logger.info(f"kNN [{self.current_epoch}/{self.num_epochs}]\tAcc@1 {r['acc1']:.2f}\tAcc@5 {r['acc5']:.2f}"
+                        f"\t(k={m.k}, T={m.t}, bank {r['n_bank']}, query {r['n_query']}, {r['seconds']:.1f} s)")
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            torch.distributed.barrier()
 
     def run(self):
         num_epochs = 1 if self.args.debug else self.num_epochs
@@ -275,6 +297,7 @@ class Engine:
         while self.current_epoch < num_epochs:
             lr = float(self.optimizer.param_groups[0]["lr"])
             stats = self.train_epoch()
+            self._run_knn_monitor()
             self.scheduler.step()
             self._write_scalars(lr)
             self.current_epoch += 1
