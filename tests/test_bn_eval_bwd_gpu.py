@@ -17,6 +17,16 @@ DEV = torch.device("cuda", 0)
 TOL = 2e-5
 
 
+# Where the test bodies place their operands on the device.  tests/test_guarded_memory_gpu.py runs the same bodies with these two
+# pointed at guarded allocations (tests/guarded.py): dev() for inputs, dev_empty() for what a kernel writes.
+def dev(t):
+    return t.to(DEV)
+
+
+def dev_empty(*shape, dtype=torch.float32):
+    return torch.empty(*shape, dtype=dtype, device=DEV)
+
+
 @pytest.fixture(scope="module")
 def hip():
     from rspnet_amd import ops
@@ -42,27 +52,27 @@ def make_case(N, D, H, W, C, k, relu, use_res, Cv=None, wide=0):
     """Device inputs.  wide > 0: y, dout (and the dy output) are channel slices [wide, wide + C) of tensors 2 * wide + C wide."""
     Cv = C if Cv is None else Cv
     pg = PoolGeom(N, D, H, W, C, k, k, (0, 0, 0))
-    gamma, beta = (rnd(Cv, seed=3) + 1.5).to(DEV), (rnd(Cv, seed=4) * 0.5).to(DEV)
-    meanp, invstd = (rnd(C, seed=6) * 0.3).to(DEV), (rnd(C, seed=7) * 0.4 + 1.0).to(DEV)
-    pad = torch.zeros(C - Cv, device=DEV)
+    gamma, beta = dev(rnd(Cv, seed=3) + 1.5), dev(rnd(Cv, seed=4) * 0.5)
+    meanp, invstd = dev(rnd(C, seed=6) * 0.3), dev(rnd(C, seed=7) * 0.4 + 1.0)
+    pad = dev_empty(C - Cv).zero_()
     scale = torch.cat([gamma, pad]) * invstd
     shift = torch.cat([beta, pad]) - meanp * scale
-    y = (rnd(N, D, H, W, C, seed=1) * 2).to(DEV)
-    res = rnd(N, D, H, W, C, seed=2).to(DEV) if use_res else None
+    y = dev(rnd(N, D, H, W, C, seed=1) * 2)
+    res = dev(rnd(N, D, H, W, C, seed=2)) if use_res else None
     z = y * scale + shift + (res if use_res else 0)
     near = (z.abs() < 1e-4) & (scale != 0)
-    y = torch.where(near, y + torch.where(z >= 0, 3e-4, -3e-4) / torch.where(scale != 0, scale, torch.ones_like(scale)), y)
+    y = dev(torch.where(near, y + torch.where(z >= 0, 3e-4, -3e-4) / torch.where(scale != 0, scale, torch.ones_like(scale)), y))
     do, ho, wo = pg.out_dims
-    dout = rnd(N, do, ho, wo, C, seed=5).to(DEV)
+    dout = dev(rnd(N, do, ho, wo, C, seed=5))
     if wide:
-        yw = torch.full((N, D, H, W, C + 2 * wide), float("nan"), device=DEV)
+        yw = dev_empty((N, D, H, W, C + 2 * wide)).fill_(float("nan"))
         yw[..., wide:wide + C] = y
         y = yw[..., wide:wide + C]
-        dw = torch.full((N, do, ho, wo, C + 2 * wide), float("nan"), device=DEV)
+        dw = dev_empty((N, do, ho, wo, C + 2 * wide)).fill_(float("nan"))
         dw[..., wide:wide + C] = dout
         dout = dw[..., wide:wide + C]
-    mi = torch.stack([meanp, invstd]).contiguous()
-    ss = torch.stack([scale, shift]).contiguous()
+    mi = dev(torch.stack([meanp, invstd]).contiguous())
+    ss = dev(torch.stack([scale, shift]).contiguous())
     return pg, y, res, dout, gamma, beta, meanp, invstd, mi, ss, Cv
 
 
@@ -87,11 +97,11 @@ def reference(pg, y, res, dout, gamma, beta, meanp, invstd, relu, Cv):
 
 
 def run_op(hip, pg, y, res, dout, mi, ss, relu, Cv, sums=True, wide=0):
-    dg = torch.full((Cv,), float("nan"), device=DEV) if sums else None
-    db = torch.full((Cv,), float("nan"), device=DEV) if sums else None
+    dg = dev_empty((Cv,)).fill_(float("nan")) if sums else None
+    db = dev_empty((Cv,)).fill_(float("nan")) if sums else None
     dy_out = None
     if wide:
-        dyw = torch.full(tuple(y.shape[:4]) + (y.shape[4] + 2 * wide,), 7.0, device=DEV)
+        dyw = dev_empty(tuple(y.shape[:4]) + (y.shape[4] + 2 * wide,)).fill_(7.0)
         dy_out = dyw[..., wide:wide + y.shape[4]]
     dy, dres = hip.bn_eval_act_pool_bwd(pg, y, res, dout, mi, ss, relu, res is not None, dg, db, dy_out=dy_out)
     torch.cuda.synchronize()
@@ -173,9 +183,9 @@ def test_sums_only_for_one_parameter(hip):
     """dbeta alone (a conv-bias gradient with frozen affine parameters) or dgamma alone: the same sums as with both."""
     pg, y, res, dout, gamma, beta, meanp, invstd, mi, ss, Cv = make_case(2, 4, 8, 8, 64, (1, 2, 2), True, False)
     _, _, dg, db = run_op(hip, pg, y, None, dout, mi, ss, True, Cv)
-    db1 = torch.empty(Cv, device=DEV)
+    db1 = dev_empty(Cv)
     hip.bn_eval_act_pool_bwd(pg, y, None, dout, mi, ss, True, False, None, db1)
-    dg1 = torch.empty(Cv, device=DEV)
+    dg1 = dev_empty(Cv)
     hip.bn_eval_act_pool_bwd(pg, y, None, dout, mi, ss, True, False, dg1, None)
     assert torch.equal(db1, db) and torch.equal(dg1, dg)
 

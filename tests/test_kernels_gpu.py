@@ -13,6 +13,16 @@ DEV = torch.device("cuda", 0)
 CPU = CpuOps()
 
 
+# Where the test bodies place their operands on the device.  tests/test_guarded_memory_gpu.py runs the same bodies with these two
+# pointed at guarded allocations (tests/guarded.py): dev() for inputs, dev_empty() for what a kernel writes (in-place operands too).
+def dev(t):
+    return t.to(DEV)
+
+
+def dev_empty(*shape, dtype=torch.float32):
+    return torch.empty(*shape, dtype=dtype, device=DEV)
+
+
 @pytest.fixture(scope="module")
 def hip():
     from rspnet_amd import ops
@@ -114,7 +124,7 @@ def test_conv_fwd_dgrad_wgrad(hip, case):
     b = rnd(Cout, seed=3)
     # forward (+ bias, + stat partials)
     y_ref, st_ref = CPU.conv_fwd(g, x, w, b, True)
-    xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
+    xd, wd, bd = dev(x), dev(w), dev(b)
     y, st = hip.conv_fwd(g, xd, hip.conv_pack_fwd(g, wd), bd, True)
     close(y, y_ref, 2e-5, "conv fwd")
     close(st.double().sum(0), st_ref.double().sum(0), 2e-5, "stat partials")
@@ -125,15 +135,15 @@ def test_conv_fwd_dgrad_wgrad(hip, case):
     # dgrad
     dy = rnd(*y_ref.shape, seed=4)
     dx_ref = CPU.conv_dgrad(g, dy, w)
-    dx = hip.conv_dgrad(g, dy.to(DEV), wd)
+    dx = hip.conv_dgrad(g, dev(dy), wd)
     close(dx, dx_ref, 2e-5, "dgrad")
     # wgrad (+ dbias)
     dw_ref = torch.empty_like(w)
     db_ref = torch.empty_like(b)
     CPU.conv_wgrad(g, x, dy, dw_ref, db_ref)
-    dw = torch.empty_like(wd)
-    db = torch.empty_like(bd)
-    hip.conv_wgrad(g, xd, dy.to(DEV), dw, db)
+    dw = dev_empty(wd.shape)
+    db = dev_empty(bd.shape)
+    hip.conv_wgrad(g, xd, dev(dy), dw, db)
     close(dw, dw_ref, 2e-5, "wgrad")
     close(db, db_ref, 2e-5, "dbias")
 
@@ -169,13 +179,13 @@ def test_conv_tall_and_narrow32_instances(hip, case):
     y_ref, st_ref = CPU.conv_fwd(g, x, w, b, True)
     dy = rnd(*y_ref.shape, seed=24)
     dx_ref = CPU.conv_dgrad(g, dy, w)
-    xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
+    xd, wd, bd = dev(x), dev(w), dev(b)
     tall = case in TALL_CASES
     # (narrow32_max_units: at these sizes the launch would otherwise count as a tiny one)
     with hip.options(**({"tall_min_tiles": 2, "narrow32_max_units": 0} if tall else {})):
         y, st = hip.conv_fwd(g, xd, hip.conv_pack_fwd(g, wd), bd, True)
         kf = hip.lib.rsp_last_conv_kernel().decode()
-        dx = hip.conv_dgrad(g, dy.to(DEV), wd)
+        dx = hip.conv_dgrad(g, dev(dy), wd)
         kd = hip.lib.rsp_last_conv_kernel().decode()
     close(y, y_ref, 2e-5, "conv fwd")
     close(st.double().sum(0), st_ref.double().sum(0), 2e-5, "stat partials")
@@ -198,14 +208,14 @@ def test_conv_two_level_summation_instance(hip):
     y64 = torch.nn.functional.conv3d(x[:1].double().permute(0, 4, 1, 2, 3), w.double(), None, s, p).permute(0, 2, 3, 4, 1)      # (first sample)
     dy = rnd(*y_ref.shape, seed=34)
     dx_ref = CPU.conv_dgrad(g, dy, w)
-    xd, wd = x.to(DEV), w.to(DEV)
+    xd, wd = dev(x), dev(w)
     wp = hip.conv_pack_fwd(g, wd)
     y1, _ = hip.conv_fwd(g, xd, wp, None, True)
     k1 = hip.lib.rsp_last_conv_kernel().decode()
     with hip.options(two_level_min_chunks=8):
         y2, st2 = hip.conv_fwd(g, xd, wp, None, True)
         k2 = hip.lib.rsp_last_conv_kernel().decode()
-        dx2 = hip.conv_dgrad(g, dy.to(DEV), wd)
+        dx2 = hip.conv_dgrad(g, dev(dy), wd)
         kd = hip.lib.rsp_last_conv_kernel().decode()
     assert "fold" not in k1 and "igemm_persist_fold_kernel<128, 128" in k2, (k1, k2, kd)
     close(y2, y_ref, 2e-5, "conv fwd (two-level)")
@@ -246,16 +256,16 @@ def test_conv_fuzz(hip, case):
     w = rnd(Cout, Cin, *k, seed=12, scale=(Cin * k[0] * k[1] * k[2]) ** -0.5)
     b = rnd(Cout, seed=13)
     y_ref, st_ref = CPU.conv_fwd(g, x, w, b, True)
-    xd, wd = x.to(DEV), w.to(DEV)
-    y, st = hip.conv_fwd(g, xd, hip.conv_pack_fwd(g, wd), b.to(DEV), True)
+    xd, wd = dev(x), dev(w)
+    y, st = hip.conv_fwd(g, xd, hip.conv_pack_fwd(g, wd), dev(b), True)
     close(y, y_ref, 2e-5, "conv fwd")
     close(st.double().sum(0), st_ref.double().sum(0), 5e-5, "stat partials")
     dy = rnd(*y_ref.shape, seed=14)
-    close(hip.conv_dgrad(g, dy.to(DEV), wd), CPU.conv_dgrad(g, dy, w), 2e-5, "dgrad")
+    close(hip.conv_dgrad(g, dev(dy), wd), CPU.conv_dgrad(g, dy, w), 2e-5, "dgrad")
     dw_ref, db_ref = torch.empty_like(w), torch.empty_like(b)
     CPU.conv_wgrad(g, x, dy, dw_ref, db_ref)
-    dw, db = torch.empty_like(wd), torch.empty(Cout, device=DEV)
-    hip.conv_wgrad(g, xd, dy.to(DEV), dw, db)
+    dw, db = dev_empty(wd.shape), dev_empty(Cout)
+    hip.conv_wgrad(g, xd, dev(dy), dw, db)
     close(dw, dw_ref, 2e-5, "wgrad")
     close(db, db_ref, 2e-5, "dbias")
 
@@ -291,13 +301,13 @@ def test_conv_fuzz_padded_depth(hip, case):
 
 def test_conv_is_run_to_run_deterministic(hip):
     g = ConvGeom(1, 2, 7, 7, 256, 512, (3, 3, 3), (1, 1, 1), (1, 1, 1))   # split-K path
-    x, w = rnd(1, 2, 7, 7, 256, seed=5).to(DEV), rnd(512, 256, 3, 3, 3, seed=6).to(DEV)
+    x, w = dev(rnd(1, 2, 7, 7, 256, seed=5)), dev(rnd(512, 256, 3, 3, 3, seed=6))
     wp = hip.conv_pack_fwd(g, w)
     y1, s1 = hip.conv_fwd(g, x, wp, None, True)
     y2, s2 = hip.conv_fwd(g, x, wp, None, True)
     assert torch.equal(y1, y2) and torch.equal(s1, s2)
-    dy = rnd(*y1.shape, seed=7).to(DEV)
-    a, b = torch.empty_like(w), torch.empty_like(w)
+    dy = dev(rnd(*y1.shape, seed=7))
+    a, b = dev_empty(w.shape), dev_empty(w.shape)
     hip.conv_wgrad(g, x, dy, a)
     hip.conv_wgrad(g, x, dy, b)
     assert torch.equal(a, b)
@@ -318,8 +328,8 @@ def test_bn_finalize(hip, C, tiles_rows):
         part[t, :, 1] = (blk * blk).sum(0).float()
     rm_ref, rv_ref = rm.clone(), rv.clone()
     mi_ref, ss_ref = CPU.bn_finalize(part, rows, bias, gamma, beta, 1e-5, 0.1, rm_ref, rv_ref)
-    rm_d, rv_d = rm.to(DEV), rv.to(DEV)
-    mi, ss = hip.bn_finalize(part.to(DEV), rows, bias.to(DEV), gamma.to(DEV), beta.to(DEV), 1e-5, 0.1, rm_d, rv_d)
+    rm_d, rv_d = dev_empty(rm.shape).copy_(rm), dev_empty(rv.shape).copy_(rv)
+    mi, ss = hip.bn_finalize(dev(part), rows, dev(bias), dev(gamma), dev(beta), 1e-5, 0.1, rm_d, rv_d)
     close(mi, mi_ref, 1e-5, "mean/invstd")
     close(ss, ss_ref, 1e-5, "scale/shift")
     close(rm_d, rm_ref, 1e-5, "running_mean")
@@ -372,15 +382,15 @@ def test_bn_act_pool_fwd_bwd(hip, case):
     part = torch.stack([yy.sum(0), (yy * yy).sum(0)], 1).float().unsqueeze(0)
     mi, ss = CPU.bn_finalize(part, rows, None, gamma, beta, 1e-5, 0.1, None, None)
     out_ref = CPU.bn_act_pool_fwd(pg, y, ss, res, relu)
-    yd, ssd, mid = y.to(DEV), ss.to(DEV), mi.to(DEV)
-    resd = res.to(DEV) if use_res else None
+    yd, ssd, mid = dev(y), dev(ss), dev(mi)
+    resd = dev(res) if use_res else None
     out = hip.bn_act_pool_fwd(pg, yd, ssd, resd, relu)
     close(out, out_ref, 1e-6, "bn_act_pool fwd")
     dout = rnd(*out_ref.shape, seed=5)
     dg_ref, db_ref = torch.empty(C), torch.empty(C)
     dy_ref, dres_ref = CPU.bn_act_pool_bwd(pg, y, res, dout, gamma, mi, ss, relu, use_res, dg_ref, db_ref)
-    dg, db = torch.empty(C, device=DEV), torch.empty(C, device=DEV)
-    dy, dres = hip.bn_act_pool_bwd(pg, yd, resd, dout.to(DEV), gamma.to(DEV), mid, ssd, relu, use_res, dg, db)
+    dg, db = dev_empty(C), dev_empty(C)
+    dy, dres = hip.bn_act_pool_bwd(pg, yd, resd, dev(dout), dev(gamma), mid, ssd, relu, use_res, dg, db)
     close(dy, dy_ref, 2e-5, "bn bwd dy")
     close(dg, dg_ref, 2e-5, "dgamma")
     close(db, db_ref, 2e-5, "dbeta")
@@ -394,7 +404,7 @@ def test_head_fwd_bwd(hip, B, P, C):
     w1, w2 = rnd(128, C, seed=2, scale=C ** -0.5), rnd(128, C, seed=3, scale=C ** -0.5)
     b1, b2 = rnd(128, seed=4) * 0.1, rnd(128, seed=5) * 0.1
     o1r, o2r, pr, rr = CPU.head_fwd(feat, w1, b1, w2, b2)
-    d = [t.to(DEV) for t in (feat, w1, b1, w2, b2)]
+    d = [dev(t) for t in (feat, w1, b1, w2, b2)]
     o1, o2, pooled, raw = hip.head_fwd(*d)
     close(o1, o1r, 1e-5, "head out1")
     close(o2, o2r, 1e-5, "head out2")
@@ -403,8 +413,8 @@ def test_head_fwd_bwd(hip, B, P, C):
     g1, g2 = rnd(B, 128, seed=6), rnd(B, 128, seed=7)
     ref = [torch.empty_like(w1), torch.empty_like(b1), torch.empty_like(w2), torch.empty_like(b2)]
     dfeat_ref = CPU.head_bwd(g1, g2, pr, rr, w1, w2, tuple(feat.shape), *ref)
-    out = [torch.empty_like(t, device=DEV) for t in ref]
-    dfeat = hip.head_bwd(g1.to(DEV), g2.to(DEV), pooled, raw, d[1], d[3], tuple(feat.shape), *out)
+    out = [dev_empty(t.shape) for t in ref]
+    dfeat = hip.head_bwd(dev(g1), dev(g2), pooled, raw, d[1], d[3], tuple(feat.shape), *out)
     close(dfeat, dfeat_ref, 2e-5, "dfeat")
     for a, b, n in zip(out, ref, ("dw1", "db1", "dw2", "db2")):
         close(a, b, 2e-5, n)
@@ -416,8 +426,8 @@ def test_logits_and_loss(hip, B, K):
     f = [torch.nn.functional.normalize(rnd(B, dim, seed=i), dim=1) for i in range(6)]
     queue = torch.nn.functional.normalize(rnd(dim, K, seed=9), dim=0)
     ref = CPU.logits_fwd(*f, queue, 1 / 0.07)
-    fd = [t.to(DEV) for t in f]
-    qd = queue.to(DEV)
+    fd = [dev(t) for t in f]
+    qd = dev(queue)
     out = hip.logits_fwd(*fd, qd, 1 / 0.07)
     for a, b, n in zip(out, ref, ("logits1", "logits2", "l_pos_M", "l_neg_M")):
         close(a, b, 1e-5, n)
@@ -438,7 +448,7 @@ def test_loss_weights_and_inactive_margin(hip):
     lp = torch.tensor([[5.0], [0.1], [3.0], [-1.0], [2.0], [9.0]])
     ln = torch.tensor([[1.0], [0.2], [1.0], [1.0], [2.0], [0.0]])   # rows 0 and 5 are beyond the margin
     ref = CPU.loss_fwd_bwd(l1, l2, lp, ln, 2.0, 0.7, 1.3)
-    out = hip.loss_fwd_bwd(l1.to(DEV), l2.to(DEV), lp.to(DEV), ln.to(DEV), 2.0, 0.7, 1.3)
+    out = hip.loss_fwd_bwd(dev(l1), dev(l2), dev(lp), dev(ln), 2.0, 0.7, 1.3)
     for a, b in zip(out, ref):
         close(a, b, 1e-5, "weighted loss")
 
@@ -446,29 +456,29 @@ def test_loss_weights_and_inactive_margin(hip):
 def test_queue_enqueue_and_rows_gather(hip):
     q = rnd(128, 64, seed=1)
     keys = rnd(8, 128, seed=2)
-    qd = q.to(DEV)
-    hip.queue_enqueue(qd, 24, keys.to(DEV))
+    qd = dev_empty(q.shape).copy_(q)
+    hip.queue_enqueue(qd, 24, dev(keys))
     CPU.queue_enqueue(q, 24, keys)
     assert torch.equal(qd.cpu(), q)
     x = rnd(16, 256, seed=3)
     idx = torch.tensor([3, 3, 0, 15, 7], dtype=torch.int32)
-    assert torch.equal(hip.rows_gather(x.to(DEV), idx.to(DEV)).cpu(), CPU.rows_gather(x, idx))
+    assert torch.equal(hip.rows_gather(dev(x), dev(idx)).cpu(), CPU.rows_gather(x, idx))
 
 
 def test_clip_gather(hip):
     im = rnd(4, 3, 32, 10, 12, seed=1)
     src = torch.tensor([2, 0, 3, 1, 2], dtype=torch.int32)
     step = torch.tensor([1, 2, 2, 1, 2], dtype=torch.int32)
-    out = hip.clip_gather(im.to(DEV), src.to(DEV), step.to(DEV), 16)
+    out = hip.clip_gather(dev(im), dev(src), dev(step), 16)
     assert torch.equal(out.cpu(), CPU.clip_gather(im, src, step, 16))
-    out4 = hip.clip_gather(im.to(DEV), src.to(DEV), step.to(DEV), 16, 4)        # zero channel padding for the stems
+    out4 = hip.clip_gather(dev(im), dev(src), dev(step), 16, 4)        # zero channel padding for the stems
     assert torch.equal(out4.cpu(), CPU.clip_gather(im, src, step, 16, 4))
     # the step's three gathers as one launch (rsp_clip_gather_multi), 3 -> 4 channels (fast path) and as they are (per-job fallback)
     im2 = rnd(*im.shape, seed=12)
     src2 = torch.flip(src, dims=[0]).contiguous()
     jobs = [(im, src, step), (im2, src2, step), (im, src2, torch.ones_like(step))]
     for c_out in (4, None):
-        outs = hip.clip_gather_multi([(a.to(DEV), b.to(DEV), c.to(DEV)) for a, b, c in jobs], 16, c_out)
+        outs = hip.clip_gather_multi([(dev(a), dev(b), dev(c)) for a, b, c in jobs], 16, c_out)
         for o, (a, b, c) in zip(outs, jobs):
             assert torch.equal(o.cpu(), CPU.clip_gather(a, b, c, 16, c_out))
     assert float(out4[..., 3].abs().max()) == 0
@@ -477,14 +487,14 @@ def test_clip_gather(hip):
 @pytest.mark.parametrize("n", [4096, 1000003])
 def test_momentum_and_sgd(hip, n):
     k, q = rnd(n, seed=1), rnd(n, seed=2)
-    kd = k.to(DEV)
-    hip.momentum_update(kd, q.to(DEV), 0.999)
+    kd = dev_empty(k.shape).copy_(k)
+    hip.momentum_update(kd, dev(q), 0.999)
     CPU.momentum_update(k, q, 0.999)
     close(kd, k, 1e-7, "momentum")
     p, g, buf = rnd(n, seed=3), rnd(n, seed=4), rnd(n, seed=5)
     for first in (True, False):
-        pd, bd = p.to(DEV), buf.to(DEV)
-        hip.sgd_step(pd, g.to(DEV), bd, 0.05, 0.9, 1e-4, 1.0, first)
+        pd, bd = dev_empty(p.shape).copy_(p), dev_empty(buf.shape).copy_(buf)
+        hip.sgd_step(pd, dev(g), bd, 0.05, 0.9, 1e-4, 1.0, first)
         p2, b2 = p.clone(), buf.clone()
         CPU.sgd_step(p2, g, b2, 0.05, 0.9, 1e-4, 1.0, first)
         close(pd, p2, 1e-6, "sgd p")
@@ -495,9 +505,9 @@ def test_c_abi_rejects_bad_arguments(hip):
     from rspnet_amd._lib import RspError
     g = ConvGeom(1, 2, 4, 4, 8, 8, (3, 3, 3), (1, 1, 1), (1, 1, 1))
     with pytest.raises(RspError):
-        hip.conv_fwd(g, torch.zeros(1, 2, 4, 4, 8), torch.zeros(8 * 216, device=DEV), None, False)   # CPU tensor
+        hip.conv_fwd(g, torch.zeros(1, 2, 4, 4, 8), dev_empty(8 * 216).zero_(), None, False)   # CPU tensor
     with pytest.raises(RspError):
-        hip.queue_enqueue(torch.zeros(128, 64, device=DEV), 60, torch.zeros(8, 128, device=DEV))      # slab past K
+        hip.queue_enqueue(dev_empty(128, 64).zero_(), 60, dev_empty(8, 128).zero_())      # slab past K
 
 
 MAXPOOL_CASES = [
@@ -543,12 +553,12 @@ def test_maxpool_fwd_bwd(hip, case):
     pg = PoolGeom(N, D, H, W, C, k, s, p)
     x = torch.relu(rnd(N, D, H, W, C, seed=1))          # post-ReLU input: exact-zero ties exercise "first maximum"
     o_ref, i_ref = CPU.maxpool_fwd(pg, x, True)
-    o, idx = hip.maxpool_fwd(pg, x.to(DEV), True)
+    o, idx = hip.maxpool_fwd(pg, dev(x), True)
     assert torch.equal(o.cpu(), o_ref)
     assert torch.equal(idx.cpu(), i_ref)
     dout = rnd(*o_ref.shape, seed=2)
-    close(hip.maxpool_bwd(pg, dout.to(DEV), idx), CPU.maxpool_bwd(pg, dout, i_ref), 1e-6, "maxpool bwd")
-    o2, none = hip.maxpool_fwd(pg, x.to(DEV), False)
+    close(hip.maxpool_bwd(pg, dev(dout), idx), CPU.maxpool_bwd(pg, dout, i_ref), 1e-6, "maxpool bwd")
+    o2, none = hip.maxpool_fwd(pg, dev(x), False)
     assert none is None and torch.equal(o2.cpu(), o_ref)
 
 
@@ -558,9 +568,9 @@ def test_gate_fwd_bwd_and_channel_slices(hip, N, P, C):
     w, b = rnd(C, C, 1, 1, 1, seed=2, scale=C ** -0.5), rnd(C, seed=3)
     o_ref, m_ref, g_ref = CPU.gate_fwd(x, w, b)
     # write into a channel slice of a wider tensor, as the inception concat does
-    wide = torch.zeros(N, P, 1, 1, C + 40, device=DEV)
+    wide = dev_empty(N, P, 1, 1, C + 40).zero_()
     view = wide[..., 24:24 + C]
-    o, mean, gate = hip.gate_fwd(x.to(DEV), w.to(DEV), b.to(DEV), out=view)
+    o, mean, gate = hip.gate_fwd(dev(x), dev(w), dev(b), out=view)
     close(view, o_ref, 1e-5, "gate out (slice)")
     assert float(wide[..., :24].abs().max()) == 0 and float(wide[..., 24 + C:].abs().max()) == 0
     close(mean, m_ref, 1e-5, "gate mean")
@@ -568,8 +578,8 @@ def test_gate_fwd_bwd_and_channel_slices(hip, N, P, C):
     dwide = rnd(N, P, 1, 1, C + 40, seed=4)
     dw_ref, db_ref = torch.empty_like(w), torch.empty_like(b)
     dx_ref = CPU.gate_bwd(x, dwide[..., 24:24 + C], w, m_ref, g_ref, dw_ref, db_ref)
-    dw, db = torch.empty_like(w, device=DEV), torch.empty_like(b, device=DEV)
-    dx = hip.gate_bwd(x.to(DEV), dwide.to(DEV)[..., 24:24 + C], w.to(DEV), mean, gate, dw, db)
+    dw, db = dev_empty(w.shape), dev_empty(b.shape)
+    dx = hip.gate_bwd(dev(x), dev(dwide)[..., 24:24 + C], dev(w), mean, gate, dw, db)
     close(dx, dx_ref, 2e-5, "gate dx")
     close(dw, dw_ref, 2e-5, "gate dw")
     close(db, db_ref, 2e-5, "gate db")
@@ -585,15 +595,15 @@ def test_bn_act_pool_channel_slices(hip):
     part = torch.stack([yy.sum(0), (yy * yy).sum(0)], 1).float().unsqueeze(0)
     mi, ss = CPU.bn_finalize(part, rows, None, gamma, beta, 1e-3, 0.001, None, None)
     out_ref = CPU.bn_act_pool_fwd(pg, y, ss, None, True)
-    wide = torch.zeros(N, D, H, W, C + 16, device=DEV)
-    hip.bn_act_pool_fwd(pg, y.to(DEV), ss.to(DEV), None, True, out=wide[..., 16:])
+    wide = dev_empty(N, D, H, W, C + 16).zero_()
+    hip.bn_act_pool_fwd(pg, dev(y), dev(ss), None, True, out=wide[..., 16:])
     close(wide[..., 16:], out_ref, 1e-6, "sliced fwd")
     assert float(wide[..., :16].abs().max()) == 0
     dwide = rnd(N, D, H, W, C + 16, seed=5)
     dg_ref, db_ref = torch.empty(C), torch.empty(C)
     dy_ref, _ = CPU.bn_act_pool_bwd(pg, y, None, dwide[..., 16:], gamma, mi, ss, True, False, dg_ref, db_ref)
-    dg, db = torch.empty(C, device=DEV), torch.empty(C, device=DEV)
-    dy, _ = hip.bn_act_pool_bwd(pg, y.to(DEV), None, dwide.to(DEV)[..., 16:], gamma.to(DEV), mi.to(DEV), ss.to(DEV), True,
+    dg, db = dev_empty(C), dev_empty(C)
+    dy, _ = hip.bn_act_pool_bwd(pg, dev(y), None, dev(dwide)[..., 16:], dev(gamma), dev(mi), dev(ss), True,
                                 False, dg, db)
     close(dy, dy_ref, 2e-5, "sliced bwd dy")
     close(dg, dg_ref, 2e-5, "sliced dgamma")
@@ -602,26 +612,26 @@ def test_bn_act_pool_channel_slices(hip):
 def test_mlp_head_pieces(hip):
     B, C, dim = 5, 512, 128
     feat = rnd(B, 2, 3, 3, C, seed=1)
-    close(hip.spatial_mean_fwd(feat.to(DEV)), CPU.spatial_mean_fwd(feat), 1e-6, "spatial mean")
+    close(hip.spatial_mean_fwd(dev(feat)), CPU.spatial_mean_fwd(feat), 1e-6, "spatial mean")
     dm = rnd(B, C, seed=2)
-    close(hip.spatial_mean_bwd(dm.to(DEV), tuple(feat.shape)), CPU.spatial_mean_bwd(dm, tuple(feat.shape)), 1e-6, "mean bwd")
+    close(hip.spatial_mean_bwd(dev(dm), tuple(feat.shape)), CPU.spatial_mean_bwd(dm, tuple(feat.shape)), 1e-6, "mean bwd")
     x, w, b = rnd(B, C, seed=3), rnd(dim, C, seed=4, scale=C ** -0.5), rnd(dim, seed=5)
     for relu in (True, False):
         y_ref = CPU.linear_fwd(x, w, b, relu)
-        y = hip.linear_fwd(x.to(DEV), w.to(DEV), b.to(DEV), relu)
+        y = hip.linear_fwd(dev(x), dev(w), dev(b), relu)
         close(y, y_ref, 1e-5, "linear fwd")
         dy = rnd(B, dim, seed=6)
         dw_ref, db_ref = torch.empty_like(w), torch.empty_like(b)
         dx_ref = CPU.linear_bwd(x, y_ref, dy, w, relu, dw_ref, db_ref)
-        dw, db = torch.empty_like(w, device=DEV), torch.empty_like(b, device=DEV)
-        dx = hip.linear_bwd(x.to(DEV), y, dy.to(DEV), w.to(DEV), relu, dw, db)
+        dw, db = dev_empty(w.shape), dev_empty(b.shape)
+        dx = hip.linear_bwd(dev(x), y, dev(dy), dev(w), relu, dw, db)
         close(dx, dx_ref, 2e-5, "linear dx")
         close(dw, dw_ref, 2e-5, "linear dw")
         close(db, db_ref, 2e-5, "linear db")
     r = rnd(B, dim, seed=7)
-    close(hip.l2norm_fwd(r.to(DEV)), CPU.l2norm_fwd(r), 1e-6, "l2norm")
+    close(hip.l2norm_fwd(dev(r)), CPU.l2norm_fwd(r), 1e-6, "l2norm")
     g = rnd(B, dim, seed=8)
-    close(hip.l2norm_bwd(r.to(DEV), g.to(DEV)), CPU.l2norm_bwd(r, g), 2e-5, "l2norm bwd")
+    close(hip.l2norm_bwd(dev(r), dev(g)), CPU.l2norm_bwd(r, g), 2e-5, "l2norm bwd")
 
 
 # the full-size shapes whose dispatch decisions differ: slice-major / tap-major K walk, stem (resident and streaming), odd tiles,
@@ -656,8 +666,8 @@ def test_reported_kernel_name_is_the_kernel_that_ran(hip, case):
     d = g.desc()
     lib = hip.lib
     want = [lib.rsp_conv3d_kernel_name(C.byref(d), which).decode() for which in (0, 1, 2)]
-    x = torch.randn(N, D, H, W, cin, device=DEV)
-    w = torch.randn(cout, cin, *k, device=DEV) * 0.05
+    x = dev_empty(N, D, H, W, cin).copy_(torch.randn(N, D, H, W, cin, device=DEV))
+    w = dev_empty(cout, cin, *k).copy_(torch.randn(cout, cin, *k, device=DEV)) * 0.05
     if cin == 4:       # an RGB stem: packed from its three real channels, as the engine's re-pack does (the name is that instance)
         ps0 = hip.pack_set([(g, 0, w[:, :3].contiguous())])
         ps0.run()
@@ -672,7 +682,7 @@ def test_reported_kernel_name_is_the_kernel_that_ran(hip, case):
         ps.run()
         hip.conv_dgrad_packed(g, dy, ps.packed[0])
         assert lib.rsp_last_conv_kernel().decode() == want[1], ("dgrad", want[1])
-    hip.conv_wgrad(g, x, dy, torch.empty_like(w))
+    hip.conv_wgrad(g, x, dy, dev_empty(w.shape))
     assert lib.rsp_last_conv_kernel().decode() == want[2], ("wgrad", want[2])
 
 
@@ -683,11 +693,11 @@ def test_stem_skips_the_padding_channel_of_rgb_filters(hip, case):
     N, D, H, W, cin, cout, k, s, p = case
     N = 2
     g = ConvGeom(N, D, H, W, cin, cout, k, s, p)
-    x = torch.randn(N, D, H, W, cin, device=DEV)
+    x = dev_empty(N, D, H, W, cin).copy_(torch.randn(N, D, H, W, cin, device=DEV))
     x[..., 3] = 0
-    w = torch.randn(cout, cin, *k, device=DEV) * 0.05
+    w = dev_empty(cout, cin, *k).copy_(torch.randn(cout, cin, *k, device=DEV)) * 0.05
     w[:, 3] = 0
-    bias = torch.randn(cout, device=DEV)
+    bias = dev_empty(cout).copy_(torch.randn(cout, device=DEV))
     ps = hip.pack_set([(g, 0, w[:, :3].contiguous())])
     ps.run()
     y3, st3 = hip.conv_fwd(g, x, ps.packed[0], bias, True)
@@ -710,7 +720,7 @@ def test_packed_weights_are_shared_across_input_geometries(hip):
     enc = model.encoder_q
     outs = {}
     for T, HW, B in ((16, 32, 4), (8, 32, 4), (16, 48, 2), (32, 32, 3)):
-        x = torch.from_numpy(P.clips(5, 0, (B, 3, T, HW, HW))[0]).to(DEV)
+        x = dev(torch.from_numpy(P.clips(5, 0, (B, 3, T, HW, HW))[0]))
         a, m = enc(x)
         outs[(T, HW, B)] = a
         n_entries = len(enc._packed._entries)
@@ -718,7 +728,7 @@ def test_packed_weights_are_shared_across_input_geometries(hip):
             first = n_entries
         assert n_entries == first, (T, HW, B, n_entries, first)
     # same clips again through the shared copies: identical result
-    x = torch.from_numpy(P.clips(5, 0, (4, 3, 16, 32, 32))[0]).to(DEV)
+    x = dev(torch.from_numpy(P.clips(5, 0, (4, 3, 16, 32, 32))[0]))
     a2, _ = enc(x)
     assert torch.equal(a2, outs[(16, 32, 4)])
 
@@ -734,14 +744,14 @@ def test_channel_padded_unit_uses_the_parameters_own_lengths(hip):
     wp = torch.zeros(Cp, Cin, 1, 3, 3)
     wp[:Cv] = w
     y_ref, st_ref = CPU.conv_fwd(g, x, wp, None, True)
-    y, st = hip.conv_fwd(g, x.to(DEV), hip.conv_pack_fwd(g, wp.to(DEV)), None, True)
+    y, st = hip.conv_fwd(g, dev(x), hip.conv_pack_fwd(g, dev(wp)), None, True)
     close(y, y_ref, 2e-5, "padded conv")
     gamma, beta = rnd(Cv, seed=3) + 1.5, rnd(Cv, seed=4)
     rm, rv = rnd(Cv, seed=5), rnd(Cv, seed=6) + 1.5
     rm_ref, rv_ref = rm.clone(), rv.clone()
     mi_ref, ss_ref = CPU.bn_finalize(st_ref, g.rows, None, gamma, beta, 1e-5, 0.1, rm_ref, rv_ref)
-    rm_d, rv_d = rm.to(DEV), rv.to(DEV)
-    mi, ss = hip.bn_finalize(st, g.rows, None, gamma.to(DEV), beta.to(DEV), 1e-5, 0.1, rm_d, rv_d)
+    rm_d, rv_d = dev_empty(rm.shape).copy_(rm), dev_empty(rv.shape).copy_(rv)
+    mi, ss = hip.bn_finalize(st, g.rows, None, dev(gamma), dev(beta), 1e-5, 0.1, rm_d, rv_d)
     close(ss, ss_ref, 1e-5, "scale/shift (padding: 0)")
     assert float(ss[:, Cv:].abs().max()) == 0.0
     close(rm_d, rm_ref, 1e-5, "running_mean")
@@ -752,8 +762,8 @@ def test_channel_padded_unit_uses_the_parameters_own_lengths(hip):
     dout = rnd(N, D, H, W, Cp, seed=7)
     dg_ref, db_ref = torch.empty(Cv), torch.empty(Cv)
     dy_ref, _ = CPU.bn_act_pool_bwd(pg, y_ref, None, dout, gamma, mi_ref, ss_ref, True, False, dg_ref, db_ref)
-    dg, db = torch.empty(Cv, device=DEV), torch.empty(Cv, device=DEV)
-    dy, _ = hip.bn_act_pool_bwd(pg, y, None, dout.to(DEV), gamma.to(DEV), mi, ss, True, False, dg, db)
+    dg, db = dev_empty(Cv), dev_empty(Cv)
+    dy, _ = hip.bn_act_pool_bwd(pg, y, None, dev(dout), dev(gamma), mi, ss, True, False, dg, db)
     close(dy, dy_ref, 2e-5, "dy")
     close(dg, dg_ref, 2e-5, "dgamma")
     close(db, db_ref, 2e-5, "dbeta")
@@ -761,15 +771,15 @@ def test_channel_padded_unit_uses_the_parameters_own_lengths(hip):
     # weight gradient straight into the (83, 64, ...) parameter gradient; and the temporal partner whose INPUT channels are padded
     dw_ref = torch.empty_like(w)
     CPU.conv_wgrad(g, x, dy_ref, dw_ref)
-    dw = torch.empty(Cv, Cin, 1, 3, 3, device=DEV)
-    hip.conv_wgrad(g, x.to(DEV), dy, dw)
+    dw = dev_empty(Cv, Cin, 1, 3, 3)
+    hip.conv_wgrad(g, dev(x), dy, dw)
     close(dw, dw_ref, 2e-5, "dw (output channels padded)")
     g2 = ConvGeom(N, D, H, W, Cp, 64, (3, 1, 1), (1, 1, 1), (1, 0, 0))
     dy2 = rnd(N, D, H, W, 64, seed=8)
     dw2_ref = torch.empty(64, Cv, 3, 1, 1)
     CPU.conv_wgrad(g2, out.cpu(), dy2, dw2_ref)
-    dw2 = torch.empty(64, Cv, 3, 1, 1, device=DEV)
-    hip.conv_wgrad(g2, out, dy2.to(DEV), dw2)
+    dw2 = dev_empty(64, Cv, 3, 1, 1)
+    hip.conv_wgrad(g2, out, dev(dy2), dw2)
     close(dw2, dw2_ref, 2e-5, "dw (input channels padded)")
 
 
@@ -785,10 +795,11 @@ def test_deferred_running_statistics_update(hip, C, Cv, tiles):
     gamma, beta = rnd(Cv, seed=3) + 1.5, rnd(Cv, seed=4)
     rm, rv = rnd(Cv, seed=5), rnd(Cv, seed=6) + 1.5
     other_rm, other_rv = rnd(40, seed=7), rnd(40, seed=8) + 1.5                 # a second layer in the same set
-    d = lambda t: t.to(DEV)
-    rm_a, rv_a = d(rm), d(rv)
+    d = lambda t: dev(t)
+    dio = lambda t: dev_empty(t.shape).copy_(t)      # (updated in place)
+    rm_a, rv_a = dio(rm), dio(rv)
     mi_a, ss_a = hip.bn_finalize(d(part), rows, None, d(gamma), d(beta), 1e-5, 0.1, rm_a, rv_a)
-    rm_b, rv_b, orm, orv = d(rm), d(rv), d(other_rm), d(other_rv)
+    rm_b, rv_b, orm, orv = dio(rm), dio(rv), dio(other_rm), dio(other_rv)
     ema = hip.bn_ema_set([(rm_b, rv_b, 0.1), (orm, orv, 0.25)])
     ema.stats[1].copy_(torch.stack([torch.full((40,), 2.0), torch.full((40,), 3.0)]))
     mi_b, ss_b = hip.bn_finalize(d(part), rows, None, d(gamma), d(beta), 1e-5, 0.1, None, None, batch_stats_out=ema.stats[0])
@@ -816,9 +827,9 @@ def test_virtual_pixel_stem_equals_padded_stem(hip):
 def test_bn_act_gate_fused_is_bit_identical_to_the_three_ops(hip, N, D, H, W, C, pool):
     """ops.bn_act_gate_fwd (BatchNorm-apply + ReLU + S3D-G self-gating, optionally through the max-pool behind it) against
     bn_act_pool_fwd -> gate_fwd (-> maxpool_fwd): same bits, with and without the activation kept, into a channel slice too."""
-    y = rnd(N, D, H, W, C, seed=11).to(DEV)
-    ss = torch.stack([rnd(C, seed=12).abs() + 0.5, rnd(C, seed=13) * 0.3]).contiguous().to(DEV)
-    w, b = (rnd(C, C, 1, 1, 1, seed=14) * 0.2).to(DEV), (rnd(C, seed=15) * 0.1).to(DEV)
+    y = dev(rnd(N, D, H, W, C, seed=11))
+    ss = dev(torch.stack([rnd(C, seed=12).abs() + 0.5, rnd(C, seed=13) * 0.3]).contiguous())
+    w, b = dev(rnd(C, C, 1, 1, 1, seed=14) * 0.2), dev(rnd(C, seed=15) * 0.1)
     pg = PoolGeom(N, D, H, W, C)
     a_ref = hip.bn_act_pool_fwd(pg, y, ss, None, True)
     o_ref, mean_ref, gate_ref = hip.gate_fwd(a_ref, w, b)
@@ -828,7 +839,7 @@ def test_bn_act_gate_fused_is_bit_identical_to_the_three_ops(hip, N, D, H, W, C,
     assert a2 is None and torch.equal(mean2, mean_ref) and torch.equal(gate2, gate_ref) and torch.equal(o2, o_ref)
     # into a channel slice of a wider (concat) tensor
     if C % 2 == 0:
-        cat = torch.zeros(N, D, H, W, C + 8, device=DEV)
+        cat = dev_empty(N, D, H, W, C + 8).zero_()
         hip.bn_act_gate_fwd(pg, y, ss, True, w, b, False, out=cat[..., 8:])
         assert torch.equal(cat[..., 8:], o_ref) and float(cat[..., :8].abs().max()) == 0.0
     if pool is not None:
@@ -856,8 +867,8 @@ def test_bn_act_pool_fwd_overlapping_window_equals_apply_then_maxpool(hip, N, D,
     """The ResNet stems' bn1 -> relu -> MaxPool3d(3, 2, 1) (models/resnet.py:203-207) as ONE pass over the convolution output
     (engine._pool_fusion, forwards that keep nothing): bn_act_pool_fwd with the overlapping, padded window against the unit-window
     apply followed by maxpool_fwd — same bits; and against the checker."""
-    y = rnd(N, D, H, W, C, seed=61).to(DEV)
-    ss = torch.stack([rnd(C, seed=62).abs() + 0.5, rnd(C, seed=63) * 0.3]).contiguous().to(DEV)
+    y = dev(rnd(N, D, H, W, C, seed=61))
+    ss = dev(torch.stack([rnd(C, seed=62).abs() + 0.5, rnd(C, seed=63) * 0.3]).contiguous())
     a = hip.bn_act_pool_fwd(PoolGeom(N, D, H, W, C), y, ss, None, True)
     pg = PoolGeom(N, D, H, W, C, k, s, p)
     want, _ = hip.maxpool_fwd(pg, a, False)
@@ -878,25 +889,25 @@ def test_bn_act_pool_fwd_overlapping_window_equals_apply_then_maxpool(hip, N, D,
 def test_bn_act_gate_bwd_fused_matches_the_two_ops(hip, N, D, H, W, C, sliced):
     """ops.bn_act_gate_bwd (activation recomputed from y, the gate's data gradient formed inside the BatchNorm backward kernels)
     against gate_bwd on the stored activation followed by bn_act_pool_bwd — on the device and against the checker."""
-    y = rnd(N, D, H, W, C, seed=21).to(DEV)
-    gamma = (rnd(C, seed=22).abs() + 0.5).to(DEV)
+    y = dev(rnd(N, D, H, W, C, seed=21))
+    gamma = dev(rnd(C, seed=22).abs() + 0.5)
     mean_c, var_c = y.mean(dim=(0, 1, 2, 3)), y.var(dim=(0, 1, 2, 3), unbiased=False)
     invstd = 1.0 / torch.sqrt(var_c + 1e-3)
-    beta = (rnd(C, seed=23) * 0.3).to(DEV)
-    mi = torch.stack([mean_c, invstd]).contiguous()
-    ss = torch.stack([gamma * invstd, beta - mean_c * gamma * invstd]).contiguous()
-    w, b = (rnd(C, C, 1, 1, 1, seed=24) * 0.2).to(DEV), (rnd(C, seed=25) * 0.1).to(DEV)
+    beta = dev(rnd(C, seed=23) * 0.3)
+    mi = dev(torch.stack([mean_c, invstd]).contiguous())
+    ss = dev(torch.stack([gamma * invstd, beta - mean_c * gamma * invstd]).contiguous())
+    w, b = dev(rnd(C, C, 1, 1, 1, seed=24) * 0.2), dev(rnd(C, seed=25) * 0.1)
     pg = PoolGeom(N, D, H, W, C)
     o, a, mean, gate = hip.bn_act_gate_fwd(pg, y, ss, True, w, b, True)
     if sliced:      # gradient of the gated output as a channel slice of a wider concat gradient
-        wide = rnd(N, D, H, W, C + 16, seed=26).to(DEV)
+        wide = dev(rnd(N, D, H, W, C + 16, seed=26))
         dout = wide[..., 8:8 + C]
     else:
-        dout = rnd(N, D, H, W, C, seed=26).to(DEV)
-    dw_r, db_r, dg_r, dbt_r = (torch.empty_like(t) for t in (w, b, gamma, beta))
+        dout = dev(rnd(N, D, H, W, C, seed=26))
+    dw_r, db_r, dg_r, dbt_r = (dev_empty(t.shape) for t in (w, b, gamma, beta))
     dx = hip.gate_bwd(a, dout, w, mean, gate, dw_r, db_r)
     dy_r, _ = hip.bn_act_pool_bwd(pg, y, None, dx, gamma, mi, ss, True, False, dg_r, dbt_r)
-    dw, db, dg, dbt = (torch.empty_like(t) for t in (w, b, gamma, beta))
+    dw, db, dg, dbt = (dev_empty(t.shape) for t in (w, b, gamma, beta))
     dy = hip.bn_act_gate_bwd(pg, y, dout, gamma, mi, ss, True, w, mean, gate, dg, dbt, dw, db)
     for name, got, ref in (("dy", dy, dy_r), ("dw", dw, dw_r), ("db", db, db_r), ("dgamma", dg, dg_r), ("dbeta", dbt, dbt_r)):
         close(got, ref.cpu(), 1e-6, name)
@@ -942,15 +953,15 @@ def test_rowgeom_cache_is_bounded_and_ordered(hip):
             dy = rnd(g.N, do, ho, wo, g.Cout, seed=40 + rnd_i)
             dw_ref = torch.empty(g.Cout, g.Cin, *g.k)
             CPU.conv_wgrad(g, x, dy, dw_ref, None)
-            xd, dyd = x.to(DEV), dy.to(DEV)
+            xd, dyd = dev(x), dev(dy)
             # first use on the side stream (where the engine's weight-gradient tasks run), then at once on the main stream with
             # another Cout: the cached table must not be read before its fill has finished
-            dw_side = torch.empty_like(dw_ref, device=DEV)
+            dw_side = dev_empty(dw_ref.shape)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 hip.conv_wgrad(g, xd, dyd, dw_side)
             g2 = ConvGeom(g.N, g.Di, g.Hi, g.Wi, g.Cin, 16, g.k, g.s, g.p)
-            dw2 = torch.empty(16, g.Cin, *g.k, device=DEV)
+            dw2 = dev_empty(16, g.Cin, *g.k)
             hip.conv_wgrad(g2, xd, dyd[..., :16].contiguous(), dw2)
             torch.cuda.current_stream().wait_stream(side)
             close(dw_side, dw_ref, 2e-5, "wgrad on the side stream")
@@ -977,17 +988,17 @@ def test_wgrad_without_a_kept_table_computes_its_own(hip):
         g = ConvGeom(2, 4, 6, 6, Cin, Cout, (3, 3, 3), (1, 1, 1), (1, 1, 1))
         d = g.desc()
         assert ("wgrad_dma" in lib.rsp_conv3d_kernel_name(ctypes.byref(d), 2).decode()) == streams
-        x = rnd(g.N, g.Di, g.Hi, g.Wi, Cin, seed=60 + Cin).to(DEV)
-        dy = rnd(g.N, *g.out_dims, Cout, seed=70 + Cin).to(DEV)
+        x = dev(rnd(g.N, g.Di, g.Hi, g.Wi, Cin, seed=60 + Cin))
+        dy = dev(rnd(g.N, *g.out_dims, Cout, seed=70 + Cin))
         bias = cov == Cout
-        dw_kept = torch.empty(cov, Cin, 3, 3, 3, device=DEV)
-        db_kept = torch.empty(Cout, device=DEV) if bias else None
+        dw_kept = dev_empty(cov, Cin, 3, 3, 3)
+        db_kept = dev_empty(Cout) if bias else None
         hip.conv_wgrad(g, x, dy, dw_kept, db_kept)
         assert (x.device, g.N, g.Di, g.Hi, g.Wi, g.k, g.s, g.p, Cin) in hip._rowgeom       # the call above went through a kept table
-        dw_own = torch.full_like(dw_kept, float("nan"))
-        db_own = torch.full_like(db_kept, float("nan")) if bias else None
+        dw_own = dev_empty(dw_kept.shape).fill_(float("nan"))
+        db_own = dev_empty(db_kept.shape).fill_(float("nan")) if bias else None
         wsb = int(lib.rsp_conv3d_wgrad_workspace(ctypes.byref(d)))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+        ws = dev_empty(wsb, dtype=torch.uint8)
         rc = lib.rsp_conv3d_wgrad(ctypes.byref(d), _ptr(x), _ptr(dy), _ptr(dw_own), _ptr(db_own), cov, Cin, None, _ptr(ws), wsb, _stream())
         assert rc == 0, lib.rsp_last_error()
         torch.cuda.synchronize()

@@ -18,6 +18,16 @@ DEV = torch.device("cuda", 0)
 GAP = 1e-5
 
 
+# Where the test bodies place their operands on the device.  tests/test_guarded_memory_gpu.py runs the same bodies with these two
+# pointed at guarded allocations (tests/guarded.py): dev() for inputs, dev_empty() for what a kernel writes.
+def dev(t):
+    return t.to(DEV)
+
+
+def dev_empty(*shape, dtype=torch.float32):
+    return torch.empty(*shape, dtype=dtype, device=DEV)
+
+
 def fp64_topk(q, g, k):
     """Restatement: sklearn's cosine_distances in fp64 (zero rows stay zero), ranked by distance, ties to the lower index."""
     q, g = q.astype(np.float64), g.astype(np.float64)
@@ -61,7 +71,7 @@ SHAPES = [(1, 1, 512, 1), (7, 33, 512, 5), (119, 1000, 512, 50), (64, 5000, 1024
 @pytest.mark.parametrize("Nq,Ng,D,k", SHAPES)
 def test_cosine_topk_matches_fp64(Nq, Ng, D, k):
     q, g = features(Nq, Nq, D), features(Ng + 1, Ng, D)
-    idx, dist = ops.backend().cosine_topk(torch.from_numpy(q).to(DEV), torch.from_numpy(g).to(DEV), k)
+    idx, dist = ops.backend().cosine_topk(dev(torch.from_numpy(q)), dev(torch.from_numpy(g)), k)
     excused, total = check_against_fp64(q, g, k, idx, dist)
     print(f"({Nq},{Ng},{D},{k}): {excused} of {total} positions excused")
     assert excused <= 0.5 * total      # at least half of all positions are checked index for index
@@ -71,16 +81,16 @@ def test_cosine_topk_matches_fp64(Nq, Ng, D, k):
 def test_cosine_topk_edges(Nq, Ng, D, k):
     """Ng < k (tail: -1 / +inf), D not a multiple of the 32-wide chunk, D = 2, query rows past a 64-row block."""
     q, g = features(1, Nq, D), features(2, Ng, D)
-    idx, dist = ops.backend().cosine_topk(torch.from_numpy(q).to(DEV), torch.from_numpy(g).to(DEV), k)
+    idx, dist = ops.backend().cosine_topk(dev(torch.from_numpy(q)), dev(torch.from_numpy(g)), k)
     excused, total = check_against_fp64(q, g, k, idx, dist)
     assert excused <= 0.5 * total
 
 
 def test_zero_rows_and_strided_inputs():
     q, g = features(3, 40, 512, zero_rows=(0, 17)), features(4, 700, 512, zero_rows=(3, 500))
-    wide = torch.zeros((40, 600), device=DEV)
-    wide[:, 8:520] = torch.from_numpy(q).to(DEV)
-    idx, dist = ops.backend().cosine_topk(wide[:, 8:520], torch.from_numpy(g).to(DEV), 20)
+    wide = dev_empty((40, 600)).zero_()
+    wide[:, 8:520] = dev(torch.from_numpy(q))
+    idx, dist = ops.backend().cosine_topk(wide[:, 8:520], dev(torch.from_numpy(g)), 20)
     check_against_fp64(q, g, 20, idx, dist)
     assert torch.equal(idx[0].cpu(), torch.arange(20, dtype=torch.int32)) and bool((dist[0] == 1).all())
     assert torch.equal(idx[17], idx[0])
@@ -93,7 +103,7 @@ def test_exact_ties_lower_index_first():
     for dup in (17, 300, 301, 640, 899):
         g[dup] = g[5]
     q = np.stack([g[5], g[5] * 2.0, g[100]])
-    idx, dist = ops.backend().cosine_topk(torch.from_numpy(q).to(DEV), torch.from_numpy(g).to(DEV), 8, splits=4)
+    idx, dist = ops.backend().cosine_topk(dev(torch.from_numpy(q)), dev(torch.from_numpy(g)), 8, splits=4)
     idx = idx.cpu().numpy()
     assert list(idx[0, :6]) == [5, 17, 300, 301, 640, 899]
     assert list(idx[1, :6]) == [5, 17, 300, 301, 640, 899]
@@ -102,7 +112,7 @@ def test_exact_ties_lower_index_first():
 
 def test_deterministic_across_runs_and_splits():
     lib = ops.backend().lib
-    q, g = torch.from_numpy(features(6, 300, 512)).to(DEV), torch.from_numpy(features(7, 20000, 512)).to(DEV)
+    q, g = dev(torch.from_numpy(features(6, 300, 512))), dev(torch.from_numpy(features(7, 20000, 512)))
     g[1000:1010] = g[10]          # ties across split boundaries
     ref = ops.backend().cosine_topk(q, g, 50)
     used = {lib.rsp_cosine_topk_splits(300, 20000, s) for s in (0, 1, 3, 7, 16)}
@@ -115,8 +125,8 @@ def test_deterministic_across_runs_and_splits():
 
 def test_no_nq_by_ng_allocation():
     Nq, Ng, D = 4096, 65536, 512
-    q = torch.randn(Nq, D, device=DEV)
-    g = torch.randn(Ng, D, device=DEV)
+    q = dev_empty(Nq, D).copy_(torch.randn(Nq, D, device=DEV))
+    g = dev_empty(Ng, D).copy_(torch.randn(Ng, D, device=DEV))
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats(DEV)
     base = torch.cuda.max_memory_allocated(DEV)
@@ -138,7 +148,7 @@ def _topk_fixture():
 
 def test_topk_fixture_indices_and_json(tmp_path):
     z, meta, (Xq, yq, Xg, yg) = _topk_fixture()
-    idx, dist = ops.backend().cosine_topk(torch.from_numpy(Xq).to(DEV), torch.from_numpy(Xg).to(DEV), 50)
+    idx, dist = ops.backend().cosine_topk(dev(torch.from_numpy(Xq)), dev(torch.from_numpy(Xg)), 50)
     assert np.array_equal(idx.cpu().numpy(), z["idx"])
     assert float(np.abs(dist.cpu().numpy() - z["dist"]).max()) <= 2e-6
     for split, X, y in (("train", Xg, yg), ("test", Xq, yq)):
@@ -155,7 +165,7 @@ def test_topk_hits_counts():
     idx = rng.integers(-1, 50, (300, 20)).astype(np.int32)
     yq, yg = rng.integers(0, 7, 300), rng.integers(0, 7, 50)
     ks = [1, 3, 10, 20]
-    counts = ops.backend().topk_hits(torch.from_numpy(idx).to(DEV), torch.from_numpy(yq).to(DEV), torch.from_numpy(yg).to(DEV), ks)
+    counts = ops.backend().topk_hits(dev(torch.from_numpy(idx)), dev(torch.from_numpy(yq)), dev(torch.from_numpy(yg)), ks)
     want = [int(sum(any(j >= 0 and yg[j] == yq[r] for j in idx[r, :k]) for r in range(300))) for k in ks]
     assert counts.cpu().tolist() == want
 
@@ -174,7 +184,7 @@ def _feature_case(arch):
     model = get_model_class(arch=meta["arch"])(num_classes=meta["classes"])
     model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in state.items()})
     x = P.clips(meta["seed"], 0, (meta["B"], 3, meta["n_crop"] * meta["T"], meta["HW"], meta["HW"]))[0]
-    return z, meta, model.to(DEV), torch.from_numpy(x).to(DEV)
+    return z, meta, model.to(DEV), dev(torch.from_numpy(x))
 
 
 @pytest.mark.parametrize("arch", ARCHS)
@@ -266,7 +276,7 @@ def test_retrieval_end_to_end(tmp_path):
     with torch.no_grad():
         want = []
         for (clip,), _ in train:
-            mtw(finetune.reshape_clip(clip.to(DEV), n_crop))
+            mtw(finetune.reshape_clip(dev(clip), n_crop))
             want.append(finetune.average_logits(ops.backend().spatial_mean_fwd(mtw.feat), n_crop).cpu().numpy())
     want = np.concatenate(want)
     assert Xtr.dtype == np.float64 and ytr.dtype == np.int64 and Xtr.shape == (12, 512)
