@@ -70,7 +70,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_stage2(const double* __restr
   const double n = (double)count;
   const double mean0 = s / n;                   // mean of the bias-free conv output
   double var = ss / n - mean0 * mean0;          // biased
-  var = var > 0.0 ? var : 0.0;
+  var = (var > 0.0 || var != var) ? var : 0.0;      // clamp_min(0): a NaN variance stays NaN
   // channels [Cv, C) are zero padding of the convolution (R(2+1)D's odd mid-channel counts run padded to a multiple of 4): the
   // parameter vectors hold Cv entries, the pad channels get gamma = beta = 0 and move no running statistics
   const bool valid = c < Cv;
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_one_kernel(const float* __re
   const double n = (double)count;
   const double mean0 = s / n;                   // mean of the bias-free conv output
   double var = ss / n - mean0 * mean0;          // biased
-  var = var > 0.0 ? var : 0.0;
+  var = (var > 0.0 || var != var) ? var : 0.0;      // clamp_min(0): a NaN variance stays NaN
   // channels [Cv, C) are zero padding of the convolution (R(2+1)D's odd mid-channel counts run padded to a multiple of 4): the
   // parameter vectors hold Cv entries, the pad channels get gamma = beta = 0 and move no running statistics
   const bool valid = c < Cv;
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const PoolParams p
         for (int e = 0; e < VEC; ++e) {
           float z = fmaf(v[u][e], sc[e], sh[e]);
           if (p.res) z += r[u][e];
-          best[e] = p.relu ? fmaxf(z, 0.f) : z;
+          best[e] = p.relu ? rsp_relu(z) : z;
         }
         store_vec<VEC>(p.out + (o + u * step) * d.out_ld + c, best);
       }
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const PoolParams p
       for (int e = 0; e < VEC; ++e) {
         float z = fmaf(v[e], sc[e], sh[e]);
         if (p.res) z += r[e];
-        best[e] = p.relu ? fmaxf(z, 0.f) : z;
+        best[e] = p.relu ? rsp_relu(z) : z;
       }
       store_vec<VEC>(p.out + o * d.out_ld + c, best);
     }
@@ -342,9 +342,9 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const PoolParams p
           for (int e = 0; e < VEC; ++e) {
             float z = fmaf(v[w][e], sc[e], sh[e]);
             if (p.res) z += r[w][e];
-            if (p.relu) z = fmaxf(z, 0.f);
+            if (p.relu) z = rsp_relu(z);
             if (p.gate) z *= g[e];
-            best[e] = fmaxf(best[e], z);
+            best[e] = rsp_max_nan(best[e], z);
           }
         store_vec<VEC>(p.out + o * d.out_ld + c, best);
       }
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const PoolParams p
       for (int e = 0; e < VEC; ++e) {
         float z = fmaf(v[e], sc[e], sh[e]);
         if (p.res) z += r[e];
-        best[e] = p.relu ? fmaxf(z, 0.f) : z;
+        best[e] = p.relu ? rsp_relu(z) : z;
       }
       if (p.gate) {
         const int n = fastdiv(fastdiv(fastdiv((int)o, p.dWo), p.dHo), p.dDo);
@@ -397,9 +397,9 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const PoolParams p
             for (int e = 0; e < VEC; ++e) {
               float z = fmaf(v[e], sc[e], sh[e]);
               if (p.res) z += r[e];
-              if (p.relu) z = fmaxf(z, 0.f);
+              if (p.relu) z = rsp_relu(z);
               if (p.gate) z *= g[e];      // (the gated activation is what the reference pools: models/s3dg.py:105-108)
-              best[e] = fmaxf(best[e], z);
+              best[e] = rsp_max_nan(best[e], z);
             }
           }
         }
@@ -518,8 +518,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BwdParams p) {
           for (int e = 0; e < VEC; ++e) {
             float z = fmaf(yv[u][e], sc[e], sh[e]);
             if (p.res) z += r[u][e];
-            const float zz = p.relu ? fmaxf(z, 0.f) : z;
-            const float dz = (p.relu && !(zz > 0.f)) ? 0.f : g[u][e];
+            const float zz = p.relu ? rsp_relu(z) : z;
+            const float dz = (p.relu && rsp_relu_blocks(zz)) ? 0.f : g[u][e];
             s1[e] += dz;
             s2[e] = fmaf(dz, (yv[u][e] - mean[e]) * invstd[e], s2[e]);
           }
@@ -553,12 +553,12 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BwdParams p) {
             for (int e = 0; e < VEC; ++e) {
               float z = fmaf(yv[w][e], sc[e], sh[e]);
               if (p.res) z += r[w][e];
-              const float zz = p.relu ? fmaxf(z, 0.f) : z;
-              if (zz > best[e]) { best[e] = zz; by[e] = yv[w][e]; }
+              const float zz = p.relu ? rsp_relu(z) : z;
+              if (rsp_max_takes(zz, best[e])) { best[e] = zz; by[e] = yv[w][e]; }
             }
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {
-            const float dz = (p.relu && !(best[e] > 0.f)) ? 0.f : g[e];
+            const float dz = (p.relu && rsp_relu_blocks(best[e])) ? 0.f : g[e];
             s1[e] += dz;
             s2[e] = fmaf(dz, (by[e] - mean[e]) * invstd[e], s2[e]);
           }
@@ -587,8 +587,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BwdParams p) {
             zval<VEC>(p, pos, c, sc, sh, yv, z);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
-              const float zz = p.relu ? fmaxf(z[e], 0.f) : z[e];
-              if (zz > best[e]) { best[e] = zz; by[e] = yv[e]; }
+              const float zz = p.relu ? rsp_relu(z[e]) : z[e];
+              if (rsp_max_takes(zz, best[e])) { best[e] = zz; by[e] = yv[e]; }
             }
           }
         }
@@ -598,7 +598,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BwdParams p) {
       if (p.gate) gated_grad<VEC>(p, n, c, g);
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
-        const float dz = (p.relu && !(best[e] > 0.f)) ? 0.f : g[e];
+        const float dz = (p.relu && rsp_relu_blocks(best[e])) ? 0.f : g[e];
         s1[e] += dz;
         s2[e] = fmaf(dz, (by[e] - mean[e]) * invstd[e], s2[e]);
       }
@@ -665,7 +665,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BwdParams p) {
       bool win[VEC];
       float mine[VEC];
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) { mine[e] = p.relu ? fmaxf(z[e], 0.f) : z[e]; win[e] = true; }
+      for (int e = 0; e < VEC; ++e) { mine[e] = p.relu ? rsp_relu(z[e]) : z[e]; win[e] = true; }
       const int my = ((id - od * d.sT) * d.kH + (ih - oh * d.sH)) * d.kW + (iw - ow * d.sW);
       if (d.kT * d.kH * d.kW > 1) {
         for (int kt = 0; kt < d.kT; ++kt)
@@ -678,9 +678,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BwdParams p) {
               zval<VEC>(p, pp, c, sc, sh, y2, z2);
 #pragma unroll
               for (int e = 0; e < VEC; ++e) {
-                const float v = p.relu ? fmaxf(z2[e], 0.f) : z2[e];
+                const float v = p.relu ? rsp_relu(z2[e]) : z2[e];
                 // earlier positions win ties; later ones must be strictly greater to displace us
-                if (o < my ? (v >= mine[e]) : (v > mine[e])) win[e] = false;
+                if (rsp_max_displaced(o < my, v, mine[e])) win[e] = false;
               }
             }
       }
@@ -688,7 +688,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BwdParams p) {
       float g[VEC];
       load_vec<VEC>(p.dout + op * d.out_ld + c, g);
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) dz[e] = (win[e] && !(p.relu && !(mine[e] > 0.f))) ? g[e] : 0.f;
+      for (int e = 0; e < VEC; ++e) dz[e] = (win[e] && !(p.relu && rsp_relu_blocks(mine[e]))) ? g[e] : 0.f;
     }
     float o[VEC];
 #pragma unroll
@@ -752,7 +752,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BwdParams p
         for (int e = 0; e < VEC; ++e) {
           float z = fmaf(yv[u][e], sc[e], sh[e]);
           if (p.res) z += r[u][e];
-          dz[e] = (p.relu && !(z > 0.f)) ? 0.f : g[u][e];
+          dz[e] = (p.relu && rsp_relu_blocks(z)) ? 0.f : g[u][e];
           const float xhat = (yv[u][e] - mean[e]) * invstd[e];
           ov[e] = gam[e] * invstd[e] * (dz[e] - m1[e] - xhat * m2[e]);
         }
@@ -791,15 +791,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BwdParams p
           for (int e = 0; e < VEC; ++e) {
             float z = fmaf(yv[w][e], sc[e], sh[e]);
             if (p.res) z += r[w][e];
-            const float v = p.relu ? fmaxf(z, 0.f) : z;
-            if (v > best[e]) { best[e] = v; bi[e] = w; }        // first maximum in scan order
+            const float v = p.relu ? rsp_relu(z) : z;
+            if (rsp_max_takes(v, best[e])) { best[e] = v; bi[e] = w; }        // first maximum in scan order (NaNs in the window: the last NaN)
           }
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
           float ov[VEC], dz[VEC];
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {
-            dz[e] = (bi[e] == w && !(p.relu && !(best[e] > 0.f))) ? g[e] : 0.f;
+            dz[e] = (bi[e] == w && !(p.relu && rsp_relu_blocks(best[e]))) ? g[e] : 0.f;
             const float xhat = (yv[w][e] - mean[e]) * invstd[e];
             ov[e] = gam[e] * invstd[e] * (dz[e] - m1[e] - xhat * m2[e]);
           }
@@ -820,7 +820,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BwdParams p
       zval<VEC>(p, o, c, sc, sh, yv, z);
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
-        dz[e] = (p.relu && !(z[e] > 0.f)) ? 0.f : g[e];
+        dz[e] = (p.relu && rsp_relu_blocks(z[e])) ? 0.f : g[e];
         const float xhat = (yv[e] - mean[e]) * invstd[e];
         ov[e] = gam[e] * invstd[e] * (dz[e] - m1[e] - xhat * m2[e]);
       }
@@ -846,8 +846,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BwdParams p
         zval<VEC>(p, pos, c, sc, sh, yv[wdx], zv[wdx]);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-          const float v = p.relu ? fmaxf(zv[wdx][e], 0.f) : zv[wdx][e];
-          if (v > best[e]) { best[e] = v; bi[e] = wdx; }     // first maximum in scan order
+          const float v = p.relu ? rsp_relu(zv[wdx][e]) : zv[wdx][e];
+          if (rsp_max_takes(v, best[e])) { best[e] = v; bi[e] = wdx; }     // first maximum in scan order (NaNs in the window: the last NaN)
         }
         if (++kw == d.kW) { kw = 0; if (++kh == d.kH) { kh = 0; ++kt; } }
       }
@@ -860,7 +860,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BwdParams p
         float ov[VEC], dz[VEC];
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-          dz[e] = (bi[e] == wdx && !(p.relu && !(best[e] > 0.f))) ? g[e] : 0.f;
+          dz[e] = (bi[e] == wdx && !(p.relu && rsp_relu_blocks(best[e]))) ? g[e] : 0.f;
           const float xhat = (yv[wdx][e] - mean[e]) * invstd[e];
           ov[e] = gam[e] * invstd[e] * (dz[e] - m1[e] - xhat * m2[e]);
         }
@@ -947,7 +947,7 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const EvalBwdParams p)
           for (int e = 0; e < VEC; ++e) {
             float z = fmaf(yv[u][e], sc[e], sh[e]);
             if (p.res) z += r[u][e];
-            dz[e] = (p.relu && !(z > 0.f)) ? 0.f : g[u][e];
+            dz[e] = (p.relu && rsp_relu_blocks(z)) ? 0.f : g[u][e];
             ov[e] = scd[e] * dz[e];
             if constexpr (SUMS) {
               s1[e] += dz[e];
@@ -966,7 +966,7 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const EvalBwdParams p)
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
           const float zz = fmaf(yv[e], sc[e], sh[e]) + (p.res ? z[e] : 0.f);
-          dz[e] = (p.relu && !(zz > 0.f)) ? 0.f : g[e];
+          dz[e] = (p.relu && rsp_relu_blocks(zz)) ? 0.f : g[e];
           ov[e] = scd[e] * dz[e];
           if constexpr (SUMS) {
             s1[e] += dz[e];
@@ -977,7 +977,7 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const EvalBwdParams p)
         if (p.dres) store_vec<VEC>(p.dres + o * d.res_ld + c, dz);
       }
     } else if constexpr (MODE == 2 || MODE == 3) {
-      // whole windows of 4 or 8 positions: loads first, then the arg-max (first maximum in scan order), then the stores
+      // whole windows of 4 or 8 positions: loads first, then the arg-max (first maximum in scan order; the last NaN if there is one), then the stores
       constexpr int NW = MODE == 2 ? 4 : 8;
       long long off[NW];
       window_offsets<NW>(d, off);
@@ -1003,13 +1003,13 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const EvalBwdParams p)
           for (int e = 0; e < VEC; ++e) {
             float z = fmaf(yv[w][e], sc[e], sh[e]);
             if (p.res) z += r[w][e];
-            const float v = p.relu ? fmaxf(z, 0.f) : z;
-            if (v > best[e]) { best[e] = v; bi[e] = w; by[e] = yv[w][e]; }
+            const float v = p.relu ? rsp_relu(z) : z;
+            if (rsp_max_takes(v, best[e])) { best[e] = v; bi[e] = w; by[e] = yv[w][e]; }
           }
         float dzo[VEC];
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-          dzo[e] = (p.relu && !(best[e] > 0.f)) ? 0.f : g[e];
+          dzo[e] = (p.relu && rsp_relu_blocks(best[e])) ? 0.f : g[e];
           if constexpr (SUMS) {
             s1[e] += dzo[e];
             s2[e] = fmaf(dzo[e], (by[e] - mean[e]) * invstd[e], s2[e]);
@@ -1052,8 +1052,8 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const EvalBwdParams p)
                 for (int e = 0; e < VEC; ++e) {
                   float z = fmaf(yv[e], sc[e], sh[e]);
                   if (p.res) z += r[e];
-                  const float v = p.relu ? fmaxf(z, 0.f) : z;
-                  if (v > best[e]) { best[e] = v; bi[e] = (kt * d.kH + kh) * d.kW + kw; by[e] = yv[e]; }
+                  const float v = p.relu ? rsp_relu(z) : z;
+                  if (rsp_max_takes(v, best[e])) { best[e] = v; bi[e] = (kt * d.kH + kh) * d.kW + kw; by[e] = yv[e]; }
                 }
               }
           const long long oo = (((long long)n * d.Do + od) * d.Ho + oh) * d.Wo + ow;
@@ -1061,7 +1061,7 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const EvalBwdParams p)
           load_vec<VEC>(p.dout + oo * d.out_ld + c, g);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {
-            dzo[e] = (p.relu && !(best[e] > 0.f)) ? 0.f : g[e];
+            dzo[e] = (p.relu && rsp_relu_blocks(best[e])) ? 0.f : g[e];
             if constexpr (SUMS) {
               s1[e] += dzo[e];
               s2[e] = fmaf(dzo[e], (by[e] - mean[e]) * invstd[e], s2[e]);

@@ -103,6 +103,26 @@ __device__ __forceinline__ float rsp_wave_max(float v) {
   return v;
 }
 
+// Non-finite values propagate as in the reference's torch ops (no fast-math in the build: `v != v` is the NaN test).  For operands
+// that are not NaN each helper computes what the expression it replaces computed, to the bit.
+//   rsp_max_nan        IEEE 754-2019 maximum — one v_maximum3_f32 on gfx950: NaN if either operand is NaN, else fmaxf's result
+//                      (-0 < +0 included).  The scan step of max_pool3d, `(v > best) || isnan(v)`, where only the value is kept.
+//   rsp_relu           torch.relu: maximum(z, 0), NaN stays NaN (fmaxf(NaN, 0) is 0)
+//   rsp_relu_blocks    ReLU's backward (threshold_backward): the gradient is dropped where the activation input is <= 0 — a NaN
+//                      input passes it on (`!(z > 0)` would drop it)
+//   rsp_max_takes      the same scan step for value and arg-max together: a NaN displaces whatever is held, a later NaN displaces
+//                      an earlier one, nothing else displaces a NaN
+//   rsp_max_displaced  input-centric form of the scan: whether window element `v`, scanned earlier / later than `mine`, takes the
+//                      window from `mine` (first maximum in scan order; with NaNs in the window the last NaN holds it)
+__device__ __forceinline__ float rsp_max_nan(float best, float v) { return __builtin_elementwise_maximum(best, v); }
+__device__ __forceinline__ float rsp_relu(float z) { return __builtin_elementwise_maximum(z, 0.f); }
+__device__ __forceinline__ bool rsp_relu_blocks(float z) { return z <= 0.f; }
+__device__ __forceinline__ bool rsp_max_takes(float v, float best) { return v > best || v != v; }
+__device__ __forceinline__ bool rsp_max_displaced(bool earlier, float v, float mine) {
+  const bool vn = v != v, mn = mine != mine;
+  return earlier ? (!mn && (vn || v >= mine)) : (vn || (!mn && v > mine));
+}
+
 // Division by a launch constant as multiply-high + shift (the prologue of every tile decodes 4 GEMM rows per thread into
 // (n, d, h, w) and its k position into (tap, channel): with hardware-free integer division that was ~1000 instructions
 // per wave).  Exact for 0 <= n < 2^31: mul = ceil(2^(31+s) / d), s = ceil(log2 d); q = umulhi(n, mul) >> (s - 1).

@@ -160,15 +160,15 @@ __global__ void rows_gather_kernel(const float* __restrict__ in, const int* __re
 
 // Small element-wise pieces of the 'conv' / 'speednet' projection heads (moco/split_wrapper.py:18-39,146-149) and the
 // gradient accumulation at fan-out points of the layer graph (residual / inception branches share an input).
-// op: 0 relu fwd (y = max(a,0)), 1 relu bwd (y = a > 0 ? b : 0), 2 sigmoid fwd, 3 sigmoid bwd (y = b*a*(1-a), a = sigmoid out),
+// op: 0 relu fwd (y = max(a,0), NaN stays NaN), 1 relu bwd (y = a <= 0 ? 0 : b: a NaN a hands b on, as threshold_backward), 2 sigmoid fwd, 3 sigmoid bwd (y = b*a*(1-a), a = sigmoid out),
 //     4 accumulate (y = a + b)
 // `y` may alias `a` or `b` at identical indices (the engine accumulates gradients over the fresh operand, ReLU runs in place):
 // no __restrict__ on any of the three — every thread reads index i of the inputs before it writes index i of the output.
 template <int OP>
 __global__ __launch_bounds__(256) void eltwise_kernel(const float* a, const float* b, float* y, long long n) {
   auto f = [](float u, float v) -> float {
-    if (OP == 0) return fmaxf(u, 0.f);
-    if (OP == 1) return u > 0.f ? v : 0.f;
+    if (OP == 0) return rsp_relu(u);
+    if (OP == 1) return rsp_relu_blocks(u) ? 0.f : v;
     if (OP == 2) return 1.f / (1.f + expf(-u));
     if (OP == 3) return v * u * (1.f - u);
     return u + v;

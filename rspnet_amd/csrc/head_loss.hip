@@ -46,6 +46,9 @@ __global__ __launch_bounds__(256) void head_raw_kernel(const float* __restrict__
   }
 }
 
+// F.normalize's clamp_min(norm, 1e-12): a NaN norm stays NaN (fmaxf would return the 1e-12)
+__device__ __forceinline__ float l2_clamp(float nrm) { return nrm != nrm ? nrm : fmaxf(nrm, 1e-12f); }
+
 // out_h[b][:] = raw[h][b][:] / max(|raw[h][b][:]|, 1e-12); one wave per (sample, head)
 __global__ __launch_bounds__(64) void head_norm_kernel(const float* __restrict__ raw, int B, int dim, float* __restrict__ out1,
                                                        float* __restrict__ out2) {
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(64) void head_norm_kernel(const float* __restrict__
   float ss = 0.f;
   for (int o = lane; o < dim; o += 64) ss = fmaf(r[o], r[o], ss);
   ss = rsp_wave_sum(ss);
-  const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+  const float nrm = l2_clamp(sqrtf(ss));
   float* out = (hsel ? out2 : out1) + (long long)b * dim;
   for (int o = lane; o < dim; o += 64) out[o] = r[o] / nrm;
 }
@@ -75,7 +78,7 @@ __global__ __launch_bounds__(64) void head_bwd_norm_kernel(const float* __restri
   dot = rsp_wave_sum(dot);
   const float nrm = sqrtf(ss);
   float* d = draw + ((long long)hsel * B + b) * dim;
-  if (nrm > 1e-12f) {
+  if (!(nrm <= 1e-12f)) {      // (a NaN norm takes the unclamped branch and spreads over the row)
     const float inv = 1.f / nrm;
     const float k = dot * inv * inv;  // (y.dout)/n with y = r/n  ->  r * dot / n^2 ... applied below
     for (int o = lane; o < dim; o += 64) d[o] = (g[o] - r[o] * k) * inv;
@@ -293,8 +296,8 @@ __global__ void loss_final_kernel(const float* __restrict__ row_loss, const floa
     ce1 += (double)row_loss[b];
     ce2 += (double)row_loss[B + b];
     const float v = margin - (lp[b] - ln[b]);
-    const bool act = v >= 0.f;  // clamp_min backward passes grad where input >= min
-    rk += act ? (double)v : 0.0;
+    const bool act = v >= 0.f;  // clamp_min backward passes grad where input >= min (not where it is NaN)
+    rk += (act || v != v) ? (double)v : 0.0;      // ... while clamp_min itself hands a NaN on
     dlp[b] = act ? -M / (float)B : 0.f;
     dln[b] = act ? M / (float)B : 0.f;
   }
@@ -364,13 +367,13 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict
   s = rsp_wave_sum(s);
   if (lane == 0) {
     s += bias ? bias[co] : 0.f;
-    y[o] = relu ? fmaxf(s, 0.f) : s;
+    y[o] = relu ? rsp_relu(s) : s;
   }
 }
 __global__ void linear_bwd_dz_kernel(const float* __restrict__ y, const float* __restrict__ dy, long long n, int relu,
                                      float* __restrict__ dz) {
   const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i < n) dz[i] = (relu && !(y[i] > 0.f)) ? 0.f : dy[i];
+  if (i < n) dz[i] = (relu && rsp_relu_blocks(y[i])) ? 0.f : dy[i];      // (y = relu(z): NaN where z is)
 }
 __global__ void linear_bwd_w_kernel(const float* __restrict__ dz, const float* __restrict__ x, int B, int Cin, int Cout,
                                     float* __restrict__ dw, float* __restrict__ db) {
@@ -401,7 +404,7 @@ __global__ __launch_bounds__(64) void l2norm_fwd_kernel(const float* __restrict_
   float ss = 0.f;
   for (int o = lane; o < dim; o += 64) ss = fmaf(x[(long long)b * dim + o], x[(long long)b * dim + o], ss);
   ss = rsp_wave_sum(ss);
-  const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+  const float nrm = l2_clamp(sqrtf(ss));
   for (int o = lane; o < dim; o += 64) y[(long long)b * dim + o] = x[(long long)b * dim + o] / nrm;
 }
 __global__ __launch_bounds__(64) void l2norm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, int dim,
@@ -418,7 +421,7 @@ __global__ __launch_bounds__(64) void l2norm_bwd_kernel(const float* __restrict_
   dot = rsp_wave_sum(dot);
   const float nrm = sqrtf(ss);
   float* d = dx + (long long)b * dim;
-  if (nrm > 1e-12f) {
+  if (!(nrm <= 1e-12f)) {      // (a NaN norm takes the unclamped branch and spreads over the row)
     const float inv = 1.f / nrm, k = dot * inv * inv;
     for (int o = lane; o < dim; o += 64) d[o] = (g[o] - r[o] * k) * inv;
   } else {

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const MPParams p) {
           if ((unsigned)iw >= (unsigned)d.Wi) continue;
           const int lin = (id * d.Hi + ih) * d.Wi + iw;
           const float v = p.x[((long long)n * d.Di * d.Hi * d.Wi + lin) * d.in_ld + c];
-          if (v > best || bi < 0) { best = v; bi = lin; }   // first maximum in scan order, like max_pool3d
+          if (rsp_max_takes(v, best) || bi < 0) { best = v; bi = lin; }   // first maximum in scan order (a NaN: the last one), like max_pool3d
         }
       }
     }
@@ -123,7 +123,7 @@ __device__ __forceinline__ void maxpool_fwd_vec_body(const MPParams& p, const fl
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float z = fmaf(v[t][e], sc[e], sh[e]);
-            v[t][e] = relu ? fmaxf(z, 0.f) : z;
+            v[t][e] = relu ? rsp_relu(z) : z;
           }
         if (gate) {      // S3D-G's self-gating between the activation and the pool (models/s3dg.py:105-108): per (sample, channel)
           const floatx4 gt = *reinterpret_cast<const floatx4*>(gate + (long long)n * d.C + c);
@@ -138,10 +138,10 @@ __device__ __forceinline__ void maxpool_fwd_vec_body(const MPParams& p, const fl
         if (KEEP) {
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            if (lin[t] >= 0 && (v[t][e] > best[e] || bi[e] < 0)) { best[e] = v[t][e]; bi[e] = lin[t]; }
+            if (lin[t] >= 0 && (rsp_max_takes(v[t][e], best[e]) || bi[e] < 0)) { best[e] = v[t][e]; bi[e] = lin[t]; }
         } else {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) best[e] = lin[t] >= 0 ? fmaxf(best[e], v[t][e]) : best[e];
+          for (int e = 0; e < 4; ++e) best[e] = lin[t] >= 0 ? rsp_max_nan(best[e], v[t][e]) : best[e];
         }
       }
     } else {
@@ -159,10 +159,10 @@ __device__ __forceinline__ void maxpool_fwd_vec_body(const MPParams& p, const fl
             if (KEEP) {
 #pragma unroll
               for (int e = 0; e < 4; ++e)
-                if (v[e] > best[e] || bi[e] < 0) { best[e] = v[e]; bi[e] = lin; }   // first maximum in scan order
-            } else {     // value only: same result as the tracked scan for finite inputs
+                if (rsp_max_takes(v[e], best[e]) || bi[e] < 0) { best[e] = v[e]; bi[e] = lin; }   // first maximum in scan order
+            } else {     // value only: same result as the tracked scan
 #pragma unroll
-              for (int e = 0; e < 4; ++e) best[e] = fmaxf(best[e], v[e]);
+              for (int e = 0; e < 4; ++e) best[e] = rsp_max_nan(best[e], v[e]);
             }
           }
         }
@@ -238,9 +238,9 @@ __device__ __forceinline__ ColMax mp333_column(const float* __restrict__ xn, con
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (KEEP) {
-        if (v[r][e] > m.v[e] || m.r[e] < 0) { m.v[e] = v[r][e]; m.r[e] = r; }
+        if (rsp_max_takes(v[r][e], m.v[e]) || m.r[e] < 0) { m.v[e] = v[r][e]; m.r[e] = r; }
       } else {
-        m.v[e] = fmaxf(m.v[e], v[r][e]);
+        m.v[e] = rsp_max_nan(m.v[e], v[r][e]);
       }
     }
   }
@@ -293,7 +293,9 @@ __global__ __launch_bounds__(256) void maxpool333_fwd_kernel(const MPParams p, i
           for (int kw = 0; kw < 3; ++kw) {
             const float v = col[kw]->v[e];
             const int r = col[kw]->r[e];
-            if (r >= 0 && (br < 0 || v > bv || (v == bv && r < br))) { bv = v; br = r; bk = kw; }
+            // (a column that holds a NaN reports its last one: the window's is the last of those, (kt, kh) first, then kw)
+            const bool vn = v != v, bn = bv != bv;
+            if (r >= 0 && (br < 0 || (vn ? (!bn || r >= br) : (!bn && (v > bv || (v == bv && r < br)))))) { bv = v; br = r; bk = kw; }
           }
           best[e] = bv;
           const int kt = br / 3, kh = br - kt * 3;
@@ -302,7 +304,7 @@ __global__ __launch_bounds__(256) void maxpool333_fwd_kernel(const MPParams p, i
         *reinterpret_cast<intx4*>(p.idx + (orow + w) * d.C + c) = bi;
       } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) best[e] = fmaxf(fmaxf(prev.v[e], cur.v[e]), next.v[e]);
+        for (int e = 0; e < 4; ++e) best[e] = rsp_max_nan(rsp_max_nan(prev.v[e], cur.v[e]), next.v[e]);
       }
       *reinterpret_cast<floatx4*>(p.out + (orow + w) * d.out_ld + c) = best;
       prev = cur;
@@ -463,7 +465,7 @@ __global__ __launch_bounds__(256) void bn_act_sum_kernel(const float* __restrict
     for (int pp = p0 + pl; pp < p1; pp += 4) {
       const long long row = (long long)n * P + pp;
       float z = fmaf(y[row * ld + c], sc, sh);
-      if (relu) z = fmaxf(z, 0.f);
+      if (relu) z = rsp_relu(z);
       if (act) act[row * act_ld + c] = z;
       s += z;
     }
@@ -495,7 +497,7 @@ __global__ __launch_bounds__(256) void bn_act_sum_vec_kernel(const float* __rest
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         z[e] = fmaf(v[e], sc[e], sh[e]);
-        if (relu) z[e] = fmaxf(z[e], 0.f);
+        if (relu) z[e] = rsp_relu(z[e]);
       }
       if (ap) *reinterpret_cast<floatx4*>(ap + (long long)pp * act_ld) = z;
       s += z;
@@ -527,7 +529,7 @@ __global__ __launch_bounds__(256) void dout_act_sum_kernel(const float* __restri
     for (int pp = p0 + pl; pp < p1; pp += 4) {
       const long long row = (long long)n * P + pp;
       float z = fmaf(y[row * y_ld + c], sc, sh);
-      if (relu) z = fmaxf(z, 0.f);
+      if (relu) z = rsp_relu(z);
       s = fmaf(dout[row * dout_ld + c], z, s);
     }
   }
@@ -558,7 +560,7 @@ __global__ __launch_bounds__(256) void dout_act_sum_vec_kernel(const float* __re
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float z = fmaf(v[e], sc[e], sh[e]);
-        if (relu) z = fmaxf(z, 0.f);
+        if (relu) z = rsp_relu(z);
         s[e] = fmaf(a[e], z, s[e]);
       }
     }

@@ -227,7 +227,8 @@ class CpuOps:
         return F.relu(y) if relu else y
 
     def linear_bwd(self, x, y, dy, w, relu, dw_out, db_out, want_dx=True):
-        dz = dy * (y > 0) if relu else dy
+        # ReLU's backward as torch has it (threshold_backward on the kept output: dropped where y <= 0, handed on where y is NaN)
+        dz = torch.ops.aten.threshold_backward(dy, y, 0.0) if relu else dy
         dw_out.copy_(dz.t() @ x)
         if db_out is not None:
             db_out.copy_(dz.sum(0))
@@ -303,7 +304,7 @@ class CpuOps:
         if op == "relu_fwd":
             r = F.relu(a)
         elif op == "relu_bwd":
-            r = torch.where(a > 0, b, torch.zeros_like(b))
+            r = torch.ops.aten.threshold_backward(b, a, 0.0)      # (b where a > 0 or a is NaN, else 0)
         elif op == "sigmoid_fwd":
             r = torch.sigmoid(a)
         elif op == "sigmoid_bwd":
