@@ -70,6 +70,16 @@ size_t rsp_conv3d_fwd_workspace(const rsp_conv3d_desc* d);
 int rsp_conv3d_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed, const float* bias, float* y,
                    float* stat_partials, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Forward of a stem whose output is only ever read through BatchNorm -> ReLU -> MaxPool3d(1,2,2) by a pass that keeps nothing for
+ * a backward (the key passes): instead of y, the kernel writes the maximum and the minimum of conv(x, w) + bias over each (1,2,2)
+ * window, [N][Do][Ho/2][Wo/2][Cout] each (a NaN in the window makes both NaN); stat_partials are those of rsp_conv3d_fwd, bit for
+ * bit.  BatchNorm apply and ReLU are monotone per channel, so rsp_bn_act_minmax_fwd on the pair gives what rsp_bn_act_pool_fwd gives
+ * on y.  Covered (applicable != 0): descriptors on the resident 4-channel stem kernel with 8x16 patches, even Ho and Wo, Cout a
+ * multiple of 4; w_packed is the forward-packed weight of the same descriptor. */
+int rsp_conv3d_stem_pooled_applicable(const rsp_conv3d_desc* d);
+int rsp_conv3d_stem_pooled_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed, const float* bias, float* y_max,
+                               float* y_min, float* stat_partials, void* stream);
+
 /* dgrad: dx = conv_transpose(dy, w).  Replaces autograd's conv backward-input for every conv on the path
  * (loss.backward(), pretrain.py:164).  w_ref in reference layout; packs per stride-parity class into workspace. */
 size_t rsp_conv3d_dgrad_workspace(const rsp_conv3d_desc* d);
@@ -245,6 +255,26 @@ int rsp_bn_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* r
                         const float* gamma, const float* mean_invstd, const float* scale_shift, int relu, float* dy,
                         float* dres, float* dgamma, float* dbeta, int32_t c_valid, const float* gate, const float* dmean,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* Pooled units (disjoint windows of 4 or 8 positions, no residual, no gate; C, in_ld, out_ld multiples of 4 and 16-byte aligned
+ * pointers: applicable != 0) whose forward is followed by a backward.  The forward also keeps y_sel [N][Do][Ho][Wo][C] (dense), the
+ * raw y at the position of each window the backward's arg-max rule selects; `out` is rsp_bn_act_pool_fwd's, bit for bit.  The
+ * backward's reduce pass then reads dout and y_sel instead of dout and all of y (its sums only involve the selected positions; the
+ * others contribute exact zeros), with the same partial-sum partitioning: dy, dgamma, dbeta are rsp_bn_act_pool_bwd's bit for bit.
+ * Workspace: rsp_bn_bwd_workspace(d). */
+int rsp_bn_act_pool_sel_applicable(const rsp_pool3d_desc* d);
+int rsp_bn_act_pool_sel_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, int relu, float* out, float* y_sel,
+                            void* stream);
+int rsp_bn_act_pool_sel_bwd(const rsp_pool3d_desc* d, const float* y, const float* y_sel, const float* dout, const float* gamma,
+                            const float* mean_invstd, const float* scale_shift, int relu, float* dy, float* dgamma, float* dbeta,
+                            int32_t c_valid, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Second half of a stem unit after rsp_conv3d_stem_pooled_fwd: out = act(fma(scale, scale >= 0 ? y_max : y_min, shift)) per channel
+ * over `positions` rows of C floats (out: pitch out_ld, so a channel slice of a wider tensor is a valid destination).  For scale == 0
+ * both operands are evaluated and a NaN from either (0 * +-inf) is kept.  Equal to rsp_bn_act_pool_fwd on the full-size output under
+ * ==, NaNs in the same places; the sign of a zero may differ.  Finite scales only. */
+int rsp_bn_act_minmax_fwd(const float* y_max, const float* y_min, int64_t positions, int32_t C, int32_t out_ld,
+                          const float* scale_shift, int relu, float* out, void* stream);
 
 /* Eval-mode counterpart of rsp_bn_act_pool_bwd — BatchNorm on its running statistics — in ONE pass over y and dout:
  *   dz = gradient at the BatchNorm output after pool routing + ReLU mask, recomputed from y with the forward's tie rule

@@ -93,6 +93,8 @@ SIGNATURES = {
     "rsp_conv3d_stat_tiles": (_i32, [_PD]),
     "rsp_conv3d_fwd_workspace": (_sz, [_PD]),
     "rsp_conv3d_fwd": (C.c_int, [_PD, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "rsp_conv3d_stem_pooled_applicable": (C.c_int, [_PD]),
+    "rsp_conv3d_stem_pooled_fwd": (C.c_int, [_PD, _p, _p, _p, _p, _p, _p, _p]),
     "rsp_conv3d_dgrad_workspace": (_sz, [_PD]),
     "rsp_conv3d_dgrad": (C.c_int, [_PD, _p, _p, _p, _p, _sz, _p]),
     "rsp_conv3d_packed_dgrad_elems": (_sz, [_PD]),
@@ -116,6 +118,10 @@ SIGNATURES = {
     "rsp_bn_act_maxpool_fwd": (C.c_int, [_PP, _p, _p, C.c_int, _p, _p, _p, _p]),
     "rsp_bn_bwd_workspace": (_sz, [_PP]),
     "rsp_bn_act_pool_bwd": (C.c_int, [_PP, _p, _p, _p, _p, _p, _p, C.c_int, _p, _p, _p, _p, _i32, _p, _p, _p, _sz, _p]),
+    "rsp_bn_act_pool_sel_applicable": (C.c_int, [_PP]),
+    "rsp_bn_act_pool_sel_fwd": (C.c_int, [_PP, _p, _p, C.c_int, _p, _p, _p]),
+    "rsp_bn_act_pool_sel_bwd": (C.c_int, [_PP, _p, _p, _p, _p, _p, _p, C.c_int, _p, _p, _p, _i32, _p, _sz, _p]),
+    "rsp_bn_act_minmax_fwd": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, C.c_int, _p, _p]),
     "rsp_bn_eval_bwd_workspace": (_sz, [_PP]),
     "rsp_bn_eval_act_pool_bwd": (C.c_int, [_PP, _p, _p, _p, _p, _p, C.c_int, _p, _p, _p, _p, _i32, _p, _sz, _p]),
     "rsp_maxpool3d_fwd": (C.c_int, [_PP, _p, _p, _p, _p]),

@@ -409,6 +409,122 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const PoolParams p
   }
 }
 
+// The same forward for disjoint windows of 4 / 8 positions (MODE 2 / 3, no residual, no gate) of a pass a backward follows: next to
+// `out` it keeps ysel, the raw y at the position the backward's arg-max rule selects (rsp_max_takes in scan order, as
+// bn_bwd_reduce_kernel scans), at pooled size — the backward's reduce then reads dout and ysel instead of dout and all of y
+// (bn_bwd_reduce_sel_kernel).  `out` is formed exactly as bn_act_pool_fwd_kernel forms it.
+template <int VEC, int MODE>
+__global__ __launch_bounds__(256) void bn_act_pool_sel_fwd_kernel(const PoolParams p, float* __restrict__ ysel) {
+  static_assert(MODE == 2 || MODE == 3, "disjoint windows of 4 or 8 positions");
+  const rsp_pool3d_desc& d = p.d;
+  const int t = threadIdx.x;
+  const int pl = fastdiv(t, p.dcgc);
+  const int cgi = blockIdx.y * 256 + (t - pl * p.cgc);
+  if (pl >= p.ppi || cgi >= p.cg) return;
+  const int c = cgi * VEC;
+  float sc[VEC], sh[VEC];
+  load_vec<VEC>(p.ss + c, sc);
+  load_vec<VEC>(p.ss + d.C + c, sh);
+  constexpr int NW = MODE == 2 ? 4 : 8;
+  long long off[NW];
+  window_offsets<NW>(d, off);
+  for (long long o = (long long)blockIdx.x * p.ppi + pl; o < p.npos; o += (long long)gridDim.x * p.ppi) {
+    const int op = (int)o;
+    const int q1 = fastdiv(op, p.dWo), ow = op - q1 * d.Wo;
+    const int q2 = fastdiv(q1, p.dHo), oh = q1 - q2 * d.Ho;
+    const int n = fastdiv(q2, p.dDo), od = q2 - n * d.Do;
+    const long long base = (((long long)n * d.Di + od * d.sT) * d.Hi + oh * d.sH) * d.Wi + ow * d.sW;
+    float v[NW][VEC], best[VEC], top[VEC], by[VEC];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) load_vec<VEC>(p.y + (base + off[w]) * d.in_ld + c, v[w]);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) { best[e] = -INFINITY; top[e] = -INFINITY; by[e] = 0.f; }
+#pragma unroll
+    for (int w = 0; w < NW; ++w)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        float z = fmaf(v[w][e], sc[e], sh[e]);
+        if (p.relu) z = rsp_relu(z);
+        best[e] = rsp_max_nan(best[e], z);
+        if (rsp_max_takes(z, top[e])) { top[e] = z; by[e] = v[w][e]; }
+      }
+    store_vec<VEC>(p.out + o * d.out_ld + c, best);
+    store_vec<VEC>(ysel + o * d.C + c, by);
+  }
+}
+
+// Second half of a stem unit whose convolution left the window maximum and minimum of its raw output (rsp_conv3d_stem_pooled_fwd):
+// out = act(fma(scale, scale >= 0 ? mx : mn, shift)).  BatchNorm apply and ReLU are monotone per channel (a correctly rounded fma
+// is monotone in each operand), so this is the maximum over the window of act(fma(scale, y, shift)) to the bit — what
+// bn_act_pool_fwd_kernel computes from y; a NaN in the window arrives in both operands.  Scale 0 (or NaN): y * 0 is NaN for an
+// infinite y, and an infinity of either sign sits in mx or in mn, so both products are formed and a NaN from either is kept.  Only
+// the sign of a zero may differ.  (An INFINITE scale is the one case not covered: 0 * inf at a position that is neither the
+// window's maximum nor its minimum.)
+struct MinMaxParams {
+  const float* __restrict__ mx;
+  const float* __restrict__ mn;
+  const float* __restrict__ ss;   // [2][C] scale, shift
+  float* __restrict__ out;
+  int C, out_ld, relu, cg, cgc, ppi;
+  long long npos;
+  FastDiv dcgc;
+};
+
+template <int VEC>
+__device__ __forceinline__ void minmax_act(const float (&a)[VEC], const float (&b)[VEC], const float (&sc)[VEC], const float (&sh)[VEC],
+                                           int relu, float (&o)[VEC]) {
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) {
+    float z;
+    if (sc[e] > 0.f) {
+      z = fmaf(a[e], sc[e], sh[e]);
+    } else if (sc[e] < 0.f) {
+      z = fmaf(b[e], sc[e], sh[e]);
+    } else {
+      const float z1 = fmaf(a[e], sc[e], sh[e]), z2 = fmaf(b[e], sc[e], sh[e]);
+      z = z1 != z1 ? z1 : z2;
+    }
+    o[e] = relu ? rsp_relu(z) : z;
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void bn_act_minmax_fwd_kernel(const MinMaxParams p) {
+  const int t = threadIdx.x;
+  const int pl = fastdiv(t, p.dcgc);
+  const int cgi = blockIdx.y * 256 + (t - pl * p.cgc);
+  if (pl >= p.ppi || cgi >= p.cg) return;
+  const int c = cgi * VEC;
+  float sc[VEC], sh[VEC];
+  load_vec<VEC>(p.ss + c, sc);
+  load_vec<VEC>(p.ss + p.C + c, sh);
+  // four consecutive position groups per trip, every load of a trip issued before the first use (see bn_act_pool_fwd_kernel)
+  const long long step = p.ppi;
+  const long long stride = (long long)gridDim.x * p.ppi * 4;
+  long long o = (long long)blockIdx.x * p.ppi * 4 + pl;
+  for (; o + 3 * step < p.npos; o += stride) {
+    float a[4][VEC], b[4][VEC];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      load_vec<VEC>(p.mx + (o + u * step) * p.C + c, a[u]);
+      load_vec<VEC>(p.mn + (o + u * step) * p.C + c, b[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float r[VEC];
+      minmax_act<VEC>(a[u], b[u], sc, sh, p.relu, r);
+      store_vec<VEC>(p.out + (o + u * step) * p.out_ld + c, r);
+    }
+  }
+  for (int u = 0; u < 4 && o < p.npos; ++u, o += step) {      // the last, partial group of four
+    float a[VEC], b[VEC], r[VEC];
+    load_vec<VEC>(p.mx + o * p.C + c, a);
+    load_vec<VEC>(p.mn + o * p.C + c, b);
+    minmax_act<VEC>(a, b, sc, sh, p.relu, r);
+    store_vec<VEC>(p.out + o * p.out_ld + c, r);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------------------------
@@ -437,6 +553,7 @@ struct BwdParams {
   const float* __restrict__ gate;   // nullable [N][C]
   const float* __restrict__ dmean;  // [N][C]
   float invP;
+  const float* __restrict__ ysel;   // nullable: raw y at each window's selected position, dense [N,Do,Ho,Wo,C] (bn_bwd_reduce_sel_kernel)
 };
 
 template <int VEC>
@@ -602,6 +719,78 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BwdParams p) {
         s1[e] += dz;
         s2[e] = fmaf(dz, (by[e] - mean[e]) * invstd[e], s2[e]);
       }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) { red[t][e] = s1[e]; red[t][VEC + e] = s2[e]; }
+  __syncthreads();
+  if (t < cgc) {
+    float a1[VEC], a2[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) a1[e] = a2[e] = 0.f;
+    for (int l = 0; l < ppi; ++l)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) { a1[e] += red[l * cgc + t][e]; a2[e] += red[l * cgc + t][VEC + e]; }
+    float* o = p.partial + ((long long)blockIdx.x * d.C + (cg0 + t) * VEC) * 2;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) { o[2 * e] = a1[e]; o[2 * e + 1] = a2[e]; }
+  }
+}
+
+// pass 1 of a pooled unit whose forward kept ysel (bn_act_pool_sel_fwd_kernel): the sums only involve the selected position of each
+// window, so the pass reads dout and ysel — 2/P of y's bytes instead of 1 + 1/P for windows of P positions.  The activation at the
+// selected position is recomputed from ysel by the forward's expression (the same bits as the `best` of bn_bwd_reduce_kernel), the
+// positions are walked by the same threads in the same order, and the skipped positions contribute exact zeros: partials, and
+// everything behind them, are bit-identical to bn_bwd_reduce_kernel's.  Four outputs per trip with their loads issued first.
+template <int VEC>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_sel_kernel(const BwdParams p) {
+  const rsp_pool3d_desc& d = p.d;
+  __shared__ float red[256][2 * VEC];
+  const int cg0 = blockIdx.y * 256;
+  const int cgc = min(p.cg - cg0, 256);
+  const int ppi = p.ppi;
+  const int t = threadIdx.x;
+  const int pl = fastdiv(t, p.dcgc);
+  const int cgi = cg0 + (t - pl * p.cgc);
+  const bool active = pl < ppi && (t - pl * p.cgc) < cgc;
+  const int c = cgi * VEC;
+  float s1[VEC], s2[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) s1[e] = s2[e] = 0.f;
+  if (active) {
+    float sc[VEC], sh[VEC], mean[VEC], invstd[VEC];
+    load_vec<VEC>(p.ss + c, sc);
+    load_vec<VEC>(p.ss + d.C + c, sh);
+    load_vec<VEC>(p.mi + c, mean);
+    load_vec<VEC>(p.mi + d.C + c, invstd);
+    const long long npos = (long long)d.N * d.Do * d.Ho * d.Wo;
+    const long long stride = (long long)gridDim.x * ppi;
+    long long op = (long long)blockIdx.x * ppi + pl;
+    auto add = [&](const float (&g)[VEC], const float (&by)[VEC]) {
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const float z = fmaf(by[e], sc[e], sh[e]);
+        const float best = p.relu ? rsp_relu(z) : z;
+        const float dz = (p.relu && rsp_relu_blocks(best)) ? 0.f : g[e];
+        s1[e] += dz;
+        s2[e] = fmaf(dz, (by[e] - mean[e]) * invstd[e], s2[e]);
+      }
+    };
+    for (; op + 3 * stride < npos; op += 4 * stride) {
+      float g[4][VEC], by[4][VEC];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        load_vec<VEC>(p.dout + (op + u * stride) * d.out_ld + c, g[u]);
+        load_vec<VEC>(p.ysel + (op + u * stride) * d.C + c, by[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) add(g[u], by[u]);
+    }
+    for (; op < npos; op += stride) {
+      float g[VEC], by[VEC];
+      load_vec<VEC>(p.dout + op * d.out_ld + c, g);
+      load_vec<VEC>(p.ysel + op * d.C + c, by);
+      add(g, by);
     }
   }
 #pragma unroll
@@ -1223,6 +1412,51 @@ int rsp_bn_finalize(const float* stat_partials, int32_t tiles, int32_t C, int32_
   return rsp_check_launch("bn_finalize_stage2");
 }
 
+// whether rsp_bn_act_pool_sel_fwd / the y_sel form of the backward cover this unit: disjoint windows of 4 or 8 positions on the
+// 16-byte path (the pointers' alignment is checked at the call)
+int rsp_bn_act_pool_sel_applicable(const rsp_pool3d_desc* d) {
+  if (!pool_ok(d, true)) return 0;
+  const int m = bn_mode(d, false);
+  return (m == 2 || m == 3) && d->C % 4 == 0 && d->in_ld % 4 == 0 && d->out_ld % 4 == 0 ? 1 : 0;
+}
+
+int rsp_bn_act_pool_sel_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, int relu, float* out, float* y_sel,
+                            void* stream) {
+  RSP_REQUIRE(rsp_bn_act_pool_sel_applicable(d), "rsp_bn_act_pool_sel_fwd: needs disjoint windows of 4 or 8 positions and channel counts / pitches that are multiples of 4");
+  RSP_REQUIRE(y && scale_shift && out && y_sel, "rsp_bn_act_pool_sel_fwd: null pointer");
+  RSP_REQUIRE(rsp_aligned16(y) && rsp_aligned16(out) && rsp_aligned16(scale_shift) && rsp_aligned16(y_sel),
+              "rsp_bn_act_pool_sel_fwd: pointers must be 16-byte aligned");
+  PoolParams p;
+  p.d = *d; p.y = y; p.ss = scale_shift; p.res = nullptr; p.gate = nullptr; p.out = out; p.relu = relu;
+  p.cg = d->C / 4;
+  const Layout L = make_layout(d, p.cg, 4);
+  RSP_REQUIRE(L.npos < (1ll << 31), "rsp_bn_act_pool_sel_fwd: more than 2^31 - 1 output positions");
+  set_layout(p, L);
+  if (bn_mode(d, false) == 2) hipLaunchKernelGGL((bn_act_pool_sel_fwd_kernel<4, 2>), L.grid, dim3(256), 0, (hipStream_t)stream, p, y_sel);
+  else hipLaunchKernelGGL((bn_act_pool_sel_fwd_kernel<4, 3>), L.grid, dim3(256), 0, (hipStream_t)stream, p, y_sel);
+  return rsp_check_launch("bn_act_pool_sel_fwd_kernel");
+}
+
+int rsp_bn_act_minmax_fwd(const float* y_max, const float* y_min, int64_t positions, int32_t C, int32_t out_ld,
+                          const float* scale_shift, int relu, float* out, void* stream) {
+  RSP_REQUIRE(y_max && y_min && scale_shift && out, "rsp_bn_act_minmax_fwd: null pointer");
+  RSP_REQUIRE(positions > 0 && positions < (1ll << 31) && C > 0 && out_ld >= C, "rsp_bn_act_minmax_fwd: bad size");
+  MinMaxParams p;
+  p.mx = y_max; p.mn = y_min; p.ss = scale_shift; p.out = out; p.C = C; p.out_ld = out_ld; p.relu = relu; p.npos = positions;
+  const bool vec = C % 4 == 0 && out_ld % 4 == 0 && rsp_aligned16(y_max) && rsp_aligned16(y_min) && rsp_aligned16(out) &&
+                   rsp_aligned16(scale_shift);
+  p.cg = vec ? C / 4 : C;
+  p.cgc = p.cg < 256 ? p.cg : 256;
+  p.ppi = 256 / p.cgc;
+  p.dcgc = fastdiv_make(p.cgc);
+  long long b = (positions + (long long)p.ppi * 4 - 1) / ((long long)p.ppi * 4);
+  b = b > 16384 ? 16384 : (b < 1 ? 1 : b);
+  const dim3 grid((unsigned)b, (unsigned)rsp_cdiv(p.cg, 256));
+  if (vec) hipLaunchKernelGGL(bn_act_minmax_fwd_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(bn_act_minmax_fwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  return rsp_check_launch("bn_act_minmax_fwd_kernel");
+}
+
 int rsp_bn_act_pool_fwd(const rsp_pool3d_desc* d, const float* y, const float* scale_shift, const float* residual,
                         int relu, const float* gate, float* out, void* stream) {
   RSP_REQUIRE(pool_ok(d, false), "rsp_bn_act_pool_fwd: bad descriptor");
@@ -1251,10 +1485,10 @@ size_t rsp_bn_bwd_workspace(const rsp_pool3d_desc* d) {
   return rsp_align_up((size_t)2048 * d->C * 2 * sizeof(float), 256) + (size_t)d->C * 2 * sizeof(double);
 }
 
-int rsp_bn_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
-                        const float* gamma, const float* mean_invstd, const float* scale_shift, int relu, float* dy,
-                        float* dres, float* dgamma, float* dbeta, int32_t c_valid, const float* gate, const float* dmean,
-                        void* workspace, size_t workspace_bytes, void* stream) {
+static int bn_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* y_sel, const float* residual, const float* dout,
+                           const float* gamma, const float* mean_invstd, const float* scale_shift, int relu, float* dy,
+                           float* dres, float* dgamma, float* dbeta, int32_t c_valid, const float* gate, const float* dmean,
+                           void* workspace, size_t workspace_bytes, void* stream) {
   RSP_REQUIRE(pool_ok(d, true), "rsp_bn_act_pool_bwd: needs disjoint windows (kernel == stride, no padding)");
   RSP_REQUIRE(!gate || (dmean && d->kT * d->kH * d->kW == 1 && d->sT * d->sH * d->sW == 1 && !residual),
               "rsp_bn_act_pool_bwd: a gated unit has a unit window, no residual, and needs dmean");
@@ -1289,7 +1523,14 @@ int rsp_bn_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* r
   p.nblocks = reduce_blocks(d, p.cg);
   dim3 rgrid(p.nblocks, rsp_cdiv(p.cg, 256));
   const int mode = bn_mode(d, gate != nullptr);
-  RSP_BN_LAUNCH(bn_bwd_reduce_kernel, vec, mode, rgrid, s, p);
+  if (y_sel) {
+    RSP_REQUIRE(vec && (mode == 2 || mode == 3) && !residual && rsp_aligned16(y_sel),
+                "rsp_bn_act_pool_sel_bwd: y_sel needs what rsp_bn_act_pool_sel_fwd needs, and no residual");
+    p.ysel = y_sel;
+    hipLaunchKernelGGL(bn_bwd_reduce_sel_kernel<4>, rgrid, dim3(256), 0, s, p);
+  } else {
+    RSP_BN_LAUNCH(bn_bwd_reduce_kernel, vec, mode, rgrid, s, p);
+  }
   int rc = rsp_check_launch("bn_bwd_reduce_kernel");
   if (rc != RSP_OK) return rc;
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(rsp_cdiv(d->C, FIN_CH)), dim3(1024), 0, s, p.partial, p.nblocks, d->C, c_valid, sums,
@@ -1305,6 +1546,22 @@ int rsp_bn_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* r
   if (vec) hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(grid_for(total)), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(grid_for(total)), dim3(256), 0, s, p);
   return rsp_check_launch("bn_bwd_apply_kernel");
+}
+
+int rsp_bn_act_pool_bwd(const rsp_pool3d_desc* d, const float* y, const float* residual, const float* dout,
+                        const float* gamma, const float* mean_invstd, const float* scale_shift, int relu, float* dy,
+                        float* dres, float* dgamma, float* dbeta, int32_t c_valid, const float* gate, const float* dmean,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  return bn_act_pool_bwd(d, y, nullptr, residual, dout, gamma, mean_invstd, scale_shift, relu, dy, dres, dgamma, dbeta, c_valid, gate,
+                         dmean, workspace, workspace_bytes, stream);
+}
+
+int rsp_bn_act_pool_sel_bwd(const rsp_pool3d_desc* d, const float* y, const float* y_sel, const float* dout, const float* gamma,
+                            const float* mean_invstd, const float* scale_shift, int relu, float* dy, float* dgamma, float* dbeta,
+                            int32_t c_valid, void* workspace, size_t workspace_bytes, void* stream) {
+  RSP_REQUIRE(y_sel, "rsp_bn_act_pool_sel_bwd: null pointer");
+  return bn_act_pool_bwd(d, y, y_sel, nullptr, dout, gamma, mean_invstd, scale_shift, relu, dy, nullptr, dgamma, dbeta, c_valid, nullptr,
+                         nullptr, workspace, workspace_bytes, stream);
 }
 
 // ---- eval-mode backward (one pass) ---------------------------------------------------------------------------------

@@ -2759,6 +2759,19 @@ int rsp_conv3d_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_pack
   return run_igemm(p, vec4, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int rsp_conv3d_stem_pooled_applicable(const rsp_conv3d_desc* d) {
+  return desc_ok(d) && rsp_stem_applicable(d) && rsp_stem_pooled_applicable(d) ? 1 : 0;
+}
+
+int rsp_conv3d_stem_pooled_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed, const float* bias, float* y_max,
+                               float* y_min, float* stat_partials, void* stream) {
+  RSP_REQUIRE(desc_ok(d), "rsp_conv3d_stem_pooled_fwd: bad descriptor");
+  RSP_REQUIRE(x && w_packed && y_max && y_min, "rsp_conv3d_stem_pooled_fwd: null pointer");
+  RSP_REQUIRE(rsp_stem_applicable(d), "rsp_conv3d_stem_pooled_fwd: descriptor not covered (rsp_conv3d_stem_pooled_applicable)");
+  rsp_note_reset();
+  return rsp_stem_pooled_fwd(d, x, w_packed, bias, y_max, y_min, stat_partials, (hipStream_t)stream);
+}
+
 // Share of the algorithmic multiply-adds (padded taps included) that the kernels launched for this descriptor execute
 // after skipping the K chunks / row chunks that are zero padding for a whole tile.  which: 0 forward, 1 dgrad, 2 wgrad.
 double rsp_conv3d_executed_fraction(const rsp_conv3d_desc* d, int which) {

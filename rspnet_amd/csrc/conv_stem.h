@@ -13,6 +13,10 @@ int rsp_stem_pack(const rsp_conv3d_desc* d, const float* w_ref, float* w_packed,
 int rsp_stem_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed, const float* bias, float* y,
                  float* stat_partials, hipStream_t s);
 const char* rsp_stem_kernel_name(const rsp_conv3d_desc* d);   // template instance rsp_stem_fwd launches
+// pooled instance of the resident kernel (rsp_conv3d_stem_pooled_fwd): window maximum and minimum of the raw output, no y
+bool rsp_stem_pooled_applicable(const rsp_conv3d_desc* d);
+int rsp_stem_pooled_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed, const float* bias, float* y_max, float* y_min,
+                        float* stat_partials, hipStream_t s);
 // the re-pack entry points record whether the filters behind a packed stem weight had three input channels (RGB): rsp_stem_fwd
 // then skips the zero fourth channel's k-step
 void rsp_stem_note_packed(const void* w_packed, bool three_channels);

@@ -41,6 +41,11 @@ struct StemParams {
   int tiles_h, tiles_w, tiles;
   unsigned x_bytes, w_bytes;
   int wide;   // epilogue through LDS + 16-byte stores (Cout % 4 == 0, 16-byte aligned output rows and bias)
+  // pooled instance (stem_resident_kernel<..., POOL = true>): per (1,2,2) window the maximum and the minimum of the raw output,
+  // [N][Do][Ho/2][Wo/2] rows of pool_ld floats; y is not written
+  float* __restrict__ ymax;
+  float* __restrict__ ymin;
+  int pool_ld;
 };
 
 // Wide epilogue store.  A wave's 32 x 64 accumulator tile is column-per-lane (lane = output channel), so a direct store is 32
@@ -91,6 +96,46 @@ __device__ __forceinline__ void stem_store_wide(const StemParams& p, const float
         const long long addr = rowaddr[wave * 32 + 16 * r + rl];
         if (addr >= 0 && col < p.Cout) *reinterpret_cast<floatx4*>(p.y + addr + col) = v + b.w[j];
       }
+    }
+  }
+}
+
+// Pooled epilogue store (8 x 16 patches, even Ho / Wo): the output of a pass that keeps nothing for a backward is only ever read
+// through BatchNorm -> ReLU -> MaxPool(1,2,2), and a per-channel monotone map commutes with the window maximum (or minimum, for a
+// negative scale) — so the patch leaves as the window maximum AND minimum of the raw output, 2 x 1/4 of its bytes, and the full-size
+// tensor is neither written nor read back (rsp_bn_act_minmax_fwd finishes the unit).  A wave's 32 rows are two patch rows of 16
+// columns; accumulator element E is row (E >> 2) * 8 + h * 4 + (E & 3), so the four positions of window k = row / 2 are the elements
+// E0, E0 + 1, E0 + 8, E0 + 9 of ONE lane (E0 in {0, 2, 4, 6}): no cross-lane traffic.  IEEE maximum / minimum: a NaN in the window
+// makes both NaN.  The 8 windows x 64 channels of a wave go through the same 2 KB wave-private stage as the wide store, once for the
+// maxima and once for the minima, and leave as two 16-byte stores per lane and round.
+__device__ __forceinline__ void stem_store_pooled(const StemParams& p, const floatx16 (&acc)[2], float* stage /* wave-private 2 KB */,
+                                                  int n, int to, int h0, int w0, int wave, int lane, const StemBias& b) {
+  const int l32 = lane & 31, h = lane >> 5;
+  const int q = lane & 15, kr = lane >> 4;   // read side: 16 lanes per window, 4 channels each
+  long long addr[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int ho = h0 + 2 * wave, wo = w0 + 2 * (kr + 4 * i);
+    addr[i] = (ho < p.Ho && wo < p.Wo && 4 * q < p.Cout)
+                  ? ((((long long)n * p.Do + to) * (p.Ho >> 1) + (ho >> 1)) * (p.Wo >> 1) + (wo >> 1)) * p.pool_ld + 4 * q
+                  : -1;
+  }
+#pragma unroll
+  for (int o = 0; o < 2; ++o) {                // 0: maxima, 1: minima
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e0 = 0; e0 < 8; e0 += 2) {
+        const float v0 = acc[j][e0] + b.n[j], v1 = acc[j][e0 + 1] + b.n[j], v2 = acc[j][e0 + 8] + b.n[j], v3 = acc[j][e0 + 9] + b.n[j];
+        const float r = o == 0 ? __builtin_elementwise_maximum(__builtin_elementwise_maximum(v0, v1), __builtin_elementwise_maximum(v2, v3))
+                               : __builtin_elementwise_minimum(__builtin_elementwise_minimum(v0, v1), __builtin_elementwise_minimum(v2, v3));
+        stage[((e0 >> 2) * 4 + h * 2 + ((e0 & 3) >> 1)) * 64 + 32 * j + l32] = r;
+      }
+    float* dst = o == 0 ? p.ymax : p.ymin;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const floatx4 v = *reinterpret_cast<const floatx4*>(stage + (kr + 4 * i) * 64 + 4 * q);
+      if (addr[i] >= 0) *reinterpret_cast<floatx4*>(dst + addr[i]) = v;
     }
   }
 }
@@ -285,7 +330,8 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(const StemParams p) {
 // the patches with stride gridDim.x; the halo of the NEXT patch is copied (LDS-DMA) into the other halo buffer while the last
 // tap chunk of the current patch is on the matrix pipe, so a patch costs neither a weight copy nor an exposed copy latency
 // (PMC before: 46 % of the wave time parked on s_waitcnt / s_barrier).
-template <int G, bool WIDE, int NS>
+// POOL: the pooled instance (stem_store_pooled) — statistics as ever, no full-size output.
+template <int G, bool WIDE, int NS, bool POOL = false>
 __global__ __launch_bounds__(256, 2) void stem_resident_kernel(const StemParams p) {
   constexpr int TCH = 2 * G;
   constexpr int BU = TCH * 64;
@@ -419,6 +465,7 @@ __global__ __launch_bounds__(256, 2) void stem_resident_kernel(const StemParams 
     // wide form: staged through this patch's halo buffer — every wave is past its last operand read (the barrier above), and
     // the next copy into THIS buffer is issued behind the next patch's top barrier
     if (WIDE) stem_store_wide(p, acc, halo + cur * hsz + wave * 512, rowaddr, wave, lane, bias);
+    if (POOL) stem_store_pooled(p, acc, halo + cur * hsz + wave * 512, n, to, hb * TH, wb * TW, wave, lane, bias);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int col = 32 * j + l32;
@@ -428,7 +475,7 @@ __global__ __launch_bounds__(256, 2) void stem_resident_kernel(const StemParams 
       for (int e = 0; e < 16; ++e) {
         const long long addr = rowaddr[wave * 32 + (e >> 2) * 8 + h * 4 + (e & 3)];
         const float v = addr >= 0 ? acc[j][e] : 0.f;
-        if (!WIDE && addr >= 0 && col < p.Cout) p.y[addr + col] = v + bv;
+        if (!WIDE && !POOL && addr >= 0 && col < p.Cout) p.y[addr + col] = v + bv;
         s += v;
         ss = fmaf(v, v, ss);
       }
@@ -623,14 +670,12 @@ int rsp_stem_pack(const rsp_conv3d_desc* d, const float* w_ref, float* w_packed,
   return rsp_check_launch("stem_pack_kernel");
 }
 
-int rsp_stem_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed, const float* bias, float* y,
-                 float* stat_partials, hipStream_t s) {
-  const StemPlan pl = stem_plan(d);
-  RSP_REQUIRE(pl.ok, "rsp_stem_fwd: descriptor not on the stem path");
-  RSP_REQUIRE(rsp_aligned16(x) && rsp_aligned16(w_packed), "rsp_conv3d_fwd: 4-channel input and packed weight must be 16-byte aligned");
+// launch parameters of a planned stem (everything but the output pointers and the store form)
+static StemParams stem_params(const rsp_conv3d_desc* d, const StemPlan& pl, const float* x, const float* w_packed, const float* bias,
+                              float* stat_partials) {
   StemParams p;
   memset(&p, 0, sizeof p);
-  p.x = x; p.w = w_packed; p.bias = bias; p.y = y; p.stat = stat_partials;
+  p.x = x; p.w = w_packed; p.bias = bias; p.stat = stat_partials;
   p.N = d->N; p.Di = d->Di; p.Hi = d->Hi; p.Wi = d->Wi; p.Do = d->Do; p.Ho = d->Ho; p.Wo = d->Wo;
   p.kT = d->kT; p.kH = d->kH; p.kW = d->kW; p.sT = d->sT; p.sH = d->sH; p.sW = d->sW;
   p.pT = d->pT; p.pH = d->pH; p.pW = d->pW;
@@ -640,11 +685,21 @@ int rsp_stem_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed
   p.npix = pl.npix; p.npix_r = pl.npix_r; p.FR = pl.FR;
   p.ntaps = d->kT * d->kH * d->kW; p.nchunks = pl.nchunks;
   p.tiles_h = pl.tiles_h; p.tiles_w = pl.tiles_w; p.tiles = (int)pl.tiles;
+  p.x_bytes = (unsigned)((unsigned long long)d->N * d->Di * d->Hi * d->Wi * 16ull);
+  p.w_bytes = (unsigned)((size_t)pl.nchunks * pl.TCH * 1024);
+  return p;
+}
+
+int rsp_stem_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed, const float* bias, float* y,
+                 float* stat_partials, hipStream_t s) {
+  const StemPlan pl = stem_plan(d);
+  RSP_REQUIRE(pl.ok, "rsp_stem_fwd: descriptor not on the stem path");
+  RSP_REQUIRE(rsp_aligned16(x) && rsp_aligned16(w_packed), "rsp_conv3d_fwd: 4-channel input and packed weight must be 16-byte aligned");
+  StemParams p = stem_params(d, pl, x, w_packed, bias, stat_partials);
+  p.y = y;
   // wide epilogue: staged through the idle weight ring (streaming variant) or through the patch's own halo buffer (resident
   // variant — a stage of its own cost the third workgroup per CU: C3D conv1 1.02 -> 1.11 ms)
   p.wide = pl.wide_ok && rsp_aligned16(y) && (!bias || rsp_aligned16(bias));
-  p.x_bytes = (unsigned)((unsigned long long)d->N * d->Di * d->Hi * d->Wi * 16ull);
-  p.w_bytes = (unsigned)((size_t)pl.nchunks * pl.TCH * 1024);
   if (stem_three_channels(w_packed)) {
     switch (pl.G) {
       case 8: return launch_stem<8, 3>(p, pl, s);
@@ -656,5 +711,43 @@ int rsp_stem_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed
     case 8: return launch_stem<8, 4>(p, pl, s);
     case 7: return launch_stem<7, 4>(p, pl, s);
     default: return launch_stem<5, 4>(p, pl, s);
+  }
+}
+
+// ---- pooled instance -------------------------------------------------------------------------------------------------------------
+// The resident kernel on 8 x 16 patches whose halo buffer holds the 8 KB store stage (the conditions of its wide form), dense
+// 16-byte output rows, and a frame that (1,2,2) windows tile: then every window lies inside one wave's rows of one patch.
+static bool stem_pooled_ok(const rsp_conv3d_desc* d, const StemPlan& pl) {
+  return pl.ok && pl.resident && pl.wide_ok && pl.tw_shift == 4 && d->Ho % 2 == 0 && d->Wo % 2 == 0 && d->Cout % 4 == 0;
+}
+
+template <int G, int NS>
+static int launch_stem_pooled(const StemParams& p, const StemPlan& pl, hipStream_t s) {
+  long long per_cu = (160 * 1024) / (long long)pl.lds;
+  per_cu = per_cu > 3 ? 3 : per_cu;
+  const long long grid = pl.tiles < 256 * per_cu ? pl.tiles : 256 * per_cu;
+  return rsp_launch_lds<stem_resident_kernel<G, false, NS, true>>(dim3((unsigned)grid), pl.lds, 80 * 1024, s, std::tie(p),
+                                                                  "stem_resident_kernel<%d, false, %d, true>", G, NS);
+}
+
+bool rsp_stem_pooled_applicable(const rsp_conv3d_desc* d) { return stem_pooled_ok(d, stem_plan(d)); }
+
+int rsp_stem_pooled_fwd(const rsp_conv3d_desc* d, const float* x, const float* w_packed, const float* bias, float* y_max, float* y_min,
+                        float* stat_partials, hipStream_t stream) {
+  const StemPlan pl = stem_plan(d);
+  RSP_REQUIRE(stem_pooled_ok(d, pl), "rsp_conv3d_stem_pooled_fwd: descriptor not covered (rsp_conv3d_stem_pooled_applicable)");
+  RSP_REQUIRE(rsp_aligned16(x) && rsp_aligned16(w_packed) && rsp_aligned16(y_max) && rsp_aligned16(y_min),
+              "rsp_conv3d_stem_pooled_fwd: input, packed weight and both outputs must be 16-byte aligned");
+  StemParams p = stem_params(d, pl, x, w_packed, bias, stat_partials);
+  p.ymax = y_max; p.ymin = y_min; p.pool_ld = d->Cout;
+  if (stem_three_channels(w_packed)) {
+    switch (pl.G) {
+      case 7: return launch_stem_pooled<7, 3>(p, pl, stream);
+      default: return launch_stem_pooled<5, 3>(p, pl, stream);
+    }
+  }
+  switch (pl.G) {
+    case 7: return launch_stem_pooled<7, 4>(p, pl, stream);
+    default: return launch_stem_pooled<5, 4>(p, pl, stream);
   }
 }

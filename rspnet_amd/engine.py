@@ -116,6 +116,7 @@ class _Saved:
     res: Optional[torch.Tensor] = None
     eval_mode: bool = False                        # BatchNorm ran on its running statistics: mi is _eval_mean_invstd's
     gate: Optional["_SavedGate"] = None            # the self-gating unit fused behind this BatchNorm (_gate_fusion): one backward op
+    y_sel: Optional[torch.Tensor] = None           # pooled unit: y at each window's selected position (ops.bn_act_pool_sel_fwd)
 
 
 # What the other node kinds' backwards need, one record type per kind (ForwardCtx.saved).  _SavedVStem: a ConvBN that ran as two
@@ -233,6 +234,10 @@ def _adjacent_cat(ts):
 
 INPUT_CHANNEL_PAD = 4
 GATE_BWD_FUSED = not os.environ.get("RSP_NO_GATE_BWD_FUSION")      # (A/B switch for measurements)
+# (A/B switches) key passes: conv1 leaves its stem kernel pooled (_Forward.stem_pooled); query pass: pooled units keep y at the
+# selected positions and the BatchNorm backward's reduce reads that instead of y (_Forward.bn_apply)
+STEM_POOLED = not os.environ.get("RSP_NO_STEM_POOLED")
+BN_BWD_SEL = not os.environ.get("RSP_NO_BN_BWD_SEL")
 
 
 class VirtualStem:
@@ -567,6 +572,7 @@ class _Forward:
         self.pool_fusion = _pool_fusion(plan)
         self.gate_fusion = _gate_fusion(plan) if training else {}
         self.skipped = set()        # nodes that ran inside the kernel of the ConvBN in front of them
+        self.y_sel = None           # what the last bn_apply kept for the backward's reduce (_Saved.y_sel), taken by its caller
 
     def finalize(self, bn, stats, rows, bias_d):
         # deferred: {id(BatchNorm module): [2][C] buffer} — this pass reports its batch moments there and leaves the running
@@ -578,9 +584,10 @@ class _Forward:
         return self.be.bn_finalize(stats, rows, bias_d, bn.weight.data, bn.bias.data, float(bn.eps), float(bn.momentum),
                                    bn.running_mean, bn.running_var)
 
-    def bn_apply(self, node, y, ss, C, dims, xin, key=None):
+    def bn_apply(self, node, y, ss, C, dims, xin, key=None, sel=False):
         """BatchNorm apply [+ residual] [+ ReLU] [+ pool] of a convolution output y with `C` channels and dims (N, do, ho, wo)
-        -> (PoolGeom a backward needs, residual)."""
+        -> (PoolGeom a backward needs, residual).  sel: the caller stores self.y_sel in the unit's _Saved (pooled units of a kept
+        pass: y at each window's selected position, for the backward's reduce)."""
         be, slots = self.be, self.slots
         pk, ps = node.pool if node.pool else ((1, 1, 1), (1, 1, 1))
         pg = PoolGeom(*dims, C, pk, ps, (0, 0, 0))
@@ -605,6 +612,12 @@ class _Forward:
         if out is not None:
             be.bn_act_pool_fwd(pg, y, ss, res, node.relu, out=out)
         else:
+            if (sel and self.keep and self.training and BN_BWD_SEL and node.pool and res is None and pi is None
+                    and hasattr(be, "bn_act_pool_sel_fwd")):
+                got = be.bn_act_pool_sel_fwd(pg, y, ss, node.relu)
+                if got is not None:
+                    slots[node.dst], self.y_sel = got
+                    return pg, res
             slots[node.dst] = be.bn_act_pool_fwd(pg, y, ss, res, node.relu)
         return pg, res
 
@@ -642,6 +655,8 @@ class _Forward:
         bias = getattr(node.conv, "bias", None)
         bn = node.bn
         bias_d = None if bias is None else bias.data
+        if self.stem_pooled(node, key, xin, cg, bias_d):
+            return
         if self.training:
             # (no shipped backbone has a conv bias on channel-padded units; if one does, the conv needs it at the padded length)
             bias_conv = bias_d if (bias_d is None or Cp == Cout) else torch.cat([bias_d, bias_d.new_zeros(Cp - Cout)])
@@ -660,9 +675,37 @@ class _Forward:
         gated = self.gate_fusion.get(key)
         if gated is not None:
             return self.bn_gate(node, key, gated, xin, y, mi, ss, cg, dims)
-        pg, res = self.bn_apply(node, y, ss, cg.Cout, dims, xin, key)
+        pg, res = self.bn_apply(node, y, ss, cg.Cout, dims, xin, key, sel=True)
         if keep:
-            self.ctx.saved[key] = _Saved(xin, y, mi, ss, cg, pg, res, eval_mode=not self.training)
+            self.ctx.saved[key] = _Saved(xin, y, mi, ss, cg, pg, res, eval_mode=not self.training, y_sel=self.y_sel)
+            self.y_sel = None
+
+    def stem_pooled(self, node, key, xin, cg, bias_d) -> bool:
+        """A 4-channel stem with BatchNorm -> ReLU -> MaxPool(1,2,2) behind it in a training-mode pass that keeps nothing (the key
+        passes' conv1): its full-size output would be written only to be read back once and pooled to a quarter.  BatchNorm apply and
+        ReLU are monotone per channel and commute with the window maximum (minimum, for a negative scale), so the stem kernel leaves
+        the window maximum and minimum of its raw output and a small pass applies BatchNorm + ReLU to them: same values, half the
+        bytes written and a quarter read.  False where it does not apply — the caller goes on as ever."""
+        be = self.be
+        if (self.keep or not self.training or not STEM_POOLED or not node.pool or tuple(node.pool[0]) != (1, 2, 2)
+                or tuple(node.pool[1]) != (1, 2, 2) or node.residual is not None or node.cout_pad or node.virtual_w
+                or xin.shape[4] != 4 or cg.Cout > 64 or self.gate_fusion.get(key) is not None or self.pool_fusion.get(key) is not None
+                or not hasattr(be, "stem_pooled_fwd")):
+            return False
+        _, ho, wo = cg.out_dims
+        if ho % 2 or wo % 2:
+            return False
+        got = be.stem_pooled_fwd(cg, xin, self.packed.get(node.conv, cg), bias_d)
+        if got is None:
+            return False
+        ymax, ymin, stats = got
+        _, ss = self.finalize(node.bn, stats, cg.rows, bias_d)
+        out = _out_view(self.slots, node.into, ymax.shape[:4], cg.Cout, xin.device)
+        if out is not None:
+            be.bn_act_minmax_fwd(ymax, ymin, ss, node.relu, out=out)
+        else:
+            self.slots[node.dst] = be.bn_act_minmax_fwd(ymax, ymin, ss, node.relu)
+        return True
 
     def bn_gate(self, node, key, gated, xin, y, mi, ss, cg, dims):
         """The rest of a ConvBN with the Gate behind it: BatchNorm-apply + self-gating (+ the max-pool behind a front-end unit, when
@@ -832,8 +875,9 @@ class _Backward:
             return self.convbn_eval(node, sv, ni)
         bn, grad_of = node.bn, self.grad_of
         dout = self.take_grad(node, sv.cg.Cout)
+        sel = {} if sv.y_sel is None else {"y_sel": sv.y_sel}
         dy, dres = self.be.bn_act_pool_bwd(sv.pg, sv.y, sv.res, dout, bn.weight.data, sv.mi, sv.ss, node.relu,
-                                           node.residual is not None, grad_of(bn.weight), grad_of(bn.bias))
+                                           node.residual is not None, grad_of(bn.weight), grad_of(bn.bias), **sel)
         self.convbn_tail(node, sv, ni, dy, dres, True)
 
     def convbn_virtual(self, node, sv, ni):

@@ -119,6 +119,12 @@ def _pack_signature(g: "ConvGeom", which: int, cout_src: int, cin_src: int):
 
 
 @functools.lru_cache(maxsize=4096)
+def _stem_pooled_ok(g: "ConvGeom") -> bool:
+    d = g.desc()
+    return bool(_lib.load().rsp_conv3d_stem_pooled_applicable(C.byref(d)))
+
+
+@functools.lru_cache(maxsize=4096)
 def _pool_plan(pg: "PoolGeom", in_ld, out_ld, res_ld):
     lib = _lib.load()
     d = pg.desc(in_ld=in_ld, out_ld=out_ld, res_ld=res_ld)
@@ -298,6 +304,38 @@ class HipOps:
         self._log("conv_fwd", g, e0, names[0])
         return out, stats
 
+    def stem_pooled_fwd(self, g: ConvGeom, x, w_packed, bias):
+        """Stem convolution of a pass that keeps nothing, when only BatchNorm -> ReLU -> MaxPool(1,2,2) reads its output: the kernel
+        leaves the window maximum and minimum of the raw output (a quarter of its size each) instead of the output itself —
+        (y_max, y_min, stats) with the stats of conv_fwd, or None where the shape is not covered
+        (rsp_conv3d_stem_pooled_applicable; the caller runs conv_fwd then).  bn_act_minmax_fwd finishes the unit."""
+        _chk(x, "x")
+        d, dref, tiles, _, _, _, (do, ho, wo), names = _conv_plan(g, None, None)
+        if not _stem_pooled_ok(g) or x.data_ptr() % 16:
+            return None
+        ymax = torch.empty((g.N, do, ho // 2, wo // 2, g.Cout), dtype=torch.float32, device=x.device)
+        ymin = torch.empty_like(ymax)
+        stats = torch.empty((tiles, g.Cout, 2), dtype=torch.float32, device=x.device)
+        e0 = self._ev()
+        _lib.check(self.lib.rsp_conv3d_stem_pooled_fwd(dref, _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(ymax), _ptr(ymin), _ptr(stats),
+                                                       _stream()), "rsp_conv3d_stem_pooled_fwd")
+        self._log("conv_fwd", g, e0, names[0])
+        return ymax, ymin, stats
+
+    def bn_act_minmax_fwd(self, ymax, ymin, scale_shift, relu: bool, out=None):
+        """BatchNorm apply (+ ReLU) of a unit whose window maximum / minimum stem_pooled_fwd left: what bn_act_pool_fwd gives on the
+        full-size output (==, NaNs in the same places).  out: as bn_act_pool_fwd's."""
+        _chk(ymax, "ymax")
+        _chk(ymin, "ymin")
+        if out is None:
+            out = torch.empty_like(ymax)
+        Cc = ymax.shape[-1]
+        e0 = self._ev()
+        _lib.check(self.lib.rsp_bn_act_minmax_fwd(_ptr(ymax), _ptr(ymin), ymax.numel() // Cc, Cc, _rows_ld(out, "out"), _ptr(scale_shift),
+                                                  int(relu), _ptr(out), _stream()), "rsp_bn_act_minmax_fwd")
+        self._log_hbm("bn_act_pool_fwd", 4 * (2 * ymax.numel() + out.numel()), e0)
+        return out
+
     def conv_dgrad(self, g: ConvGeom, dy, w_ref):
         _chk(dy, "dy")
         _chk(w_ref, "w_ref")
@@ -447,6 +485,22 @@ class HipOps:
         self._log_hbm("bn_act_pool_fwd", 4 * (n_in * (1 if residual is None else 2) + out.numel()), e0)
         return out
 
+    def bn_act_pool_sel_fwd(self, pg: PoolGeom, y, scale_shift, relu: bool):
+        """bn_act_pool_fwd of a pooled unit (disjoint windows of 4 or 8 positions, no residual) whose backward follows: (out, y_sel)
+        with out as bn_act_pool_fwd's and y_sel the raw y at each window's selected position, which bn_act_pool_bwd takes as
+        `y_sel` to read a pooled-size tensor in its reduce pass instead of all of y — or None where the shape is not covered."""
+        in_ld = _rows_ld(y, "y")
+        d, dref, _, (do, ho, wo) = _pool_plan(pg, in_ld, None, None)
+        if not self.lib.rsp_bn_act_pool_sel_applicable(dref) or y.data_ptr() % 16 or scale_shift.data_ptr() % 16:
+            return None
+        out = torch.empty((pg.N, do, ho, wo, pg.C), dtype=torch.float32, device=y.device)
+        ysel = torch.empty_like(out)
+        e0 = self._ev()
+        _lib.check(self.lib.rsp_bn_act_pool_sel_fwd(dref, _ptr(y), _ptr(scale_shift), int(relu), _ptr(out), _ptr(ysel), _stream()),
+                   "rsp_bn_act_pool_sel_fwd")
+        self._log_hbm("bn_act_pool_fwd", 4 * (pg.N * pg.Di * pg.Hi * pg.Wi * pg.C + 2 * out.numel()), e0)
+        return out, ysel
+
     def bn_act_maxpool_fwd(self, pg: PoolGeom, y, scale_shift, relu: bool, keep: bool):
         """BatchNorm apply (+ ReLU) and an OVERLAPPING max-pool (the ResNet stems' 3x3x3 / 2 / 1) in one pass over the convolution
         output, with the arg-max a backward needs (keep) — (out, idx | None), or None when the shape is not covered
@@ -465,8 +519,9 @@ class HipOps:
         return out, idx
 
     def bn_act_pool_bwd(self, pg: PoolGeom, y, residual, dout, gamma, mean_invstd, scale_shift, relu: bool,
-                        want_dres: bool, dgamma_out, dbeta_out, dy_out=None):
-        """dy_out: where to write dy (same channel pitch as y — a slice of a wider gradient tensor when y is a slice)."""
+                        want_dres: bool, dgamma_out, dbeta_out, dy_out=None, y_sel=None):
+        """dy_out: where to write dy (same channel pitch as y — a slice of a wider gradient tensor when y is a slice).
+        y_sel: what bn_act_pool_sel_fwd kept for this unit; the reduce pass then reads it instead of y (same bits)."""
         in_ld = _rows_ld(y, "y")
         d, dref, wsb, _ = _pool_plan(pg, in_ld, _rows_ld(dout, "dout"), None if residual is None else _rows_ld(residual, "residual"))
         dy = _dy_target(y, in_ld, dy_out)
@@ -474,12 +529,21 @@ class HipOps:
         ws = self._workspace(y.device, wsb)
         c_valid = pg.C if gamma is None else int(gamma.shape[0])      # < C: zero-padded channels (gamma / dgamma / dbeta are short)
         e0 = self._ev()
+        n_in = y.numel()
+        if y_sel is not None:
+            if residual is not None or want_dres:
+                raise _lib.RspError("bn_act_pool_bwd: y_sel with a residual")
+            _lib.check(self.lib.rsp_bn_act_pool_sel_bwd(dref, _ptr(y), _ptr(_chk(y_sel, "y_sel")), _ptr(dout), _ptr(gamma), _ptr(mean_invstd),
+                                                        _ptr(scale_shift), int(relu), _ptr(dy), _ptr(dgamma_out), _ptr(dbeta_out), c_valid,
+                                                        _ptr(ws), wsb, _stream()), "rsp_bn_act_pool_sel_bwd")
+            # reduce pass: y_sel + dout read; apply pass: y + dout read, dy written
+            self._log_hbm("bn_bwd(reduce+apply)", 4 * (y_sel.numel() + 2 * dout.numel() + 2 * n_in), e0)
+            return dy, dres
         _lib.check(self.lib.rsp_bn_act_pool_bwd(dref, _ptr(y), _ptr(residual), _ptr(dout), _ptr(gamma),
                                                 _ptr(mean_invstd), _ptr(scale_shift), int(relu), _ptr(dy), _ptr(dres),
                                                 _ptr(dgamma_out), _ptr(dbeta_out), c_valid, None, None, _ptr(ws), wsb, _stream()),
                    "rsp_bn_act_pool_bwd")
         # reduce pass: y (+ residual) + dout read; apply pass: the same again, dy (+ dres) written
-        n_in = y.numel()
         self._log_hbm("bn_bwd(reduce+apply)", 4 * (2 * (n_in * (1 if residual is None else 2) + dout.numel()) + n_in * (2 if want_dres else 1)), e0)
         return dy, dres
 
