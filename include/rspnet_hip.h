@@ -456,7 +456,7 @@ int rsp_augment_batch(const rsp_augment_clip_desc* descs, int32_t n_clips, int32
                       size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
- * Video retrieval search (retrieval.hip; the reference's retrieval.py:150-176).
+ * Video retrieval search (cos_search.hip, retrieval.hip; the reference's retrieval.py:150-176).
  * q (Nq x D, row pitch ldq) and g (Ng x D, row pitch ldg): fp32 row-major, D and the pitches even, 8-byte aligned bases.
  * Writes for every query the k (1..64) nearest gallery rows by cosine distance d = clip(1 - q.g / (|q| |g|), 0, 2), best
  * first: idx (Nq x k, int32) and dist (Nq x k, fp32).  Ranking: fp32 similarity descending; an exact tie goes to the lower
@@ -475,7 +475,7 @@ int rsp_topk_hits(const int32_t* idx, int32_t Nq, int32_t k, const int64_t* y_q,
                   const int32_t* ks_host, int32_t nks, int32_t* counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
- * Weighted kNN classifier (knn.hip): the monitor of a pretext run -- the k nearest labelled gallery rows of every query vote for
+ * Weighted kNN classifier (cos_search.hip, knn.hip): the monitor of a pretext run -- the k nearest labelled gallery rows of every query vote for
  * their class with weight exp(s / T); top-1 / top-5 hits of the queries' own labels.  One call, the Nq x Ng matrix never stored.
  * q, g, ldq, ldg, D, splits: as for the search above (D and the pitches even, ld >= D, 8-byte aligned bases).  1 <= k <= 256,
  * 1 <= num_classes <= 1024, T finite and >= 0.01.  y_g: Ng int64 labels; y_q: Nq int64 labels or NULL.

@@ -32,12 +32,6 @@ __device__ __forceinline__ float crop_mean(const float* __restrict__ base, int l
   return n_crop == 1 ? s : s / (float)n_crop;
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(XE_THREADS) void xent_sample_kernel(const float* __restrict__ logits, int classes, int ld, int n_crop,
                                                                  int S, const long long* __restrict__ target,
                                                                  float* __restrict__ avg_logits, float* __restrict__ dlogits,
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(XE_THREADS) void xent_sample_kernel(const float* __
     }
   }
   sum = rsp_wave_sum(sum);
-  rank = wave_sum_i(rank);
+  rank = rsp_wave_sum_i(rank);
   if (lane == 0) {
     sf[1][wave] = sum;
     si[wave] = rank;
@@ -123,8 +117,8 @@ __global__ __launch_bounds__(64) void xent_finish_kernel(const float* __restrict
     }
   }
   sum = rsp_wave_sum(sum);
-  h1 = wave_sum_i(h1);
-  h5 = wave_sum_i(h5);
+  h1 = rsp_wave_sum_i(h1);
+  h5 = rsp_wave_sum_i(h5);
   if (lane != 0) return;
   const float l = sum / (float)S;
   loss[0] = l;

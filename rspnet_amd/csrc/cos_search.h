@@ -1,0 +1,122 @@
+// Internal interface of the cosine top-k search (cos_search.hip), used by rsp_cosine_topk (retrieval.hip) and rsp_knn_classify
+// (knn.hip): the host launcher that leaves the per-split lists in the workspace, and the sorted list of a wave, which the search
+// kernel and the two merge kernels (cos_merge_kernel, knn_vote_kernel) share.  Not part of the C ABI.
+#pragma once
+#include "common.h"
+
+#include <math.h>
+
+constexpr int COS_SEARCH_MAXK = 256;      // 4 list slots of 64 ranks
+
+// The per-split lists the search left in the workspace: entry (split * Nq + row) * k + rank, sorted by rank; a list that is not
+// full (fewer than k gallery rows in the split) ends in index -1.
+struct CosLists {
+  float* val;
+  int* idx;
+  int splits;
+};
+
+// The size, k and alignment checks both entry points make on q and g; `who` is the entry point's name in the message.
+int rsp_cos_search_check(const char* who, const float* q, int ldq, int Nq, const float* g, int ldg, int Ng, int D, int k, int kmax);
+// Checks and carves the workspace (rsp_cosine_topk_workspace bytes), runs the inverse norms of q and g and then the search.
+int rsp_cos_search(const char* who, const float* q, int ldq, int Nq, const float* g, int ldg, int Ng, int D, int k, int splits,
+                   void* workspace, size_t workspace_bytes, hipStream_t s, CosLists* lists);
+
+// A wave's sorted list of k entries in S = ceil(k / 64) register slots per lane: rank r lives in slot r / 64, lane r % 64.
+// kmask: the lanes of the LAST slot that belong to the list (the slots below it are full).
+__device__ __forceinline__ unsigned long long last_slot_mask(int k, int S) {
+  const int n = k - 64 * (S - 1);
+  return n >= 64 ? ~0ull : ((1ull << n) - 1ull);
+}
+
+// Insert (s, i).  Entries already in the list that are >= s stay ahead: the caller inserts in ascending gallery index order, so on
+// an exact tie the lower index stays first.  false: s is behind all k entries.
+template <int S>
+__device__ __forceinline__ bool list_insert(float (&tv)[S], int (&ti)[S], float s, int i, int k, unsigned long long kmask, int lane) {
+  int pos = 0;
+#pragma unroll
+  for (int sl = 0; sl < S; ++sl) {
+    const unsigned long long b = __ballot(tv[sl] >= s);
+    pos += __popcll(sl == S - 1 ? (b & kmask) : b);
+  }
+  if (pos >= k) return false;
+  float bv[S];      // lane 63 of the slot below, as it was before the shift
+  int bi[S];
+#pragma unroll
+  for (int sl = 1; sl < S; ++sl) {
+    bv[sl] = __shfl(tv[sl - 1], 63);
+    bi[sl] = __shfl(ti[sl - 1], 63);
+  }
+#pragma unroll
+  for (int sl = 0; sl < S; ++sl) {
+    float uv = __shfl_up(tv[sl], 1);
+    int ui = __shfl_up(ti[sl], 1);
+    if (sl > 0 && lane == 0) {
+      uv = bv[sl];
+      ui = bi[sl];
+    }
+    const int r = 64 * sl + lane;
+    if (r > pos) {
+      tv[sl] = uv;
+      ti[sl] = ui;
+    } else if (r == pos) {
+      tv[sl] = s;
+      ti[sl] = i;
+    }
+  }
+  return true;
+}
+
+// One split's sorted list into the wave's list; stops once an entry loses (sorted: the rest of that list loses too).
+template <int S>
+__device__ __forceinline__ void merge_split(float (&tv)[S], int (&ti)[S], const float* __restrict__ pv_, const int* __restrict__ pi_,
+                                            int k, unsigned long long kmask, int lane) {
+  float pv[S];
+  int pi[S];
+#pragma unroll
+  for (int sl = 0; sl < S; ++sl) {
+    const int rk = 64 * sl + lane;
+    pv[sl] = rk < k ? pv_[rk] : -INFINITY;
+    pi[sl] = rk < k ? pi_[rk] : -1;
+  }
+#pragma unroll
+  for (int sl = 0; sl < S; ++sl) {
+    const int n = min(64, k - 64 * sl);
+    for (int j = 0; j < n; ++j) {
+      const int cj = __shfl(pi[sl], j);
+      if (cj < 0) return;                                                            // the split's list ends here
+      if (!list_insert<S>(tv, ti, __shfl(pv[sl], j), cj, k, kmask, lane)) return;
+    }
+  }
+}
+
+// Query `row`'s list over the whole gallery: the split lists merged in split order, that is in ascending gallery ranges, so a
+// tie with an earlier split's entry stays behind it.
+template <int S>
+__device__ __forceinline__ void merge_lists(float (&tv)[S], int (&ti)[S], const float* __restrict__ part_val,
+                                            const int* __restrict__ part_idx, int Nq, int row, int k, int splits, int lane) {
+  const unsigned long long kmask = last_slot_mask(k, S);
+#pragma unroll
+  for (int sl = 0; sl < S; ++sl) {
+    tv[sl] = -INFINITY;
+    ti[sl] = -1;
+  }
+  for (int s = 0; s < splits; ++s) {
+    const long long o = ((long long)s * Nq + row) * k;
+    merge_split<S>(tv, ti, part_val + o, part_idx + o, k, kmask, lane);
+  }
+}
+
+// The list as row `row` of idx / dist: distance clip(1 - s, 0, 2); an empty entry (Ng < k) is index -1 at distance +inf.
+template <int S>
+__device__ __forceinline__ void store_list(const float (&tv)[S], const int (&ti)[S], int row, int k, int lane, int* __restrict__ idx,
+                                           float* __restrict__ dist) {
+#pragma unroll
+  for (int sl = 0; sl < S; ++sl) {
+    const int rk = 64 * sl + lane;
+    if (rk < k) {
+      idx[(long long)row * k + rk] = ti[sl];
+      dist[(long long)row * k + rk] = ti[sl] < 0 ? INFINITY : fminf(fmaxf(1.f - tv[sl], 0.f), 2.f);
+    }
+  }
+}

@@ -20,12 +20,6 @@ namespace {
 constexpr int PM_THREADS = 256;
 constexpr int PM_MISS = 0x7fffffff;
 
-__device__ __forceinline__ int pm_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(PM_THREADS) void pretext_rank_kernel(const float* __restrict__ logits1,
                                                                   const float* __restrict__ logits2, int B, int K1,
                                                                   int* __restrict__ rank_out) {
@@ -45,7 +39,7 @@ __global__ __launch_bounds__(PM_THREADS) void pretext_rank_kernel(const float* _
     n += (x[0] > v0 ? 1 : 0) + (x[1] > v0 ? 1 : 0) + (x[2] > v0 ? 1 : 0) + (x[3] > v0 ? 1 : 0);
   }
   if (tail0 + t < K1) n += base[tail0 + t] > v0 ? 1 : 0;      // at most 3 columns
-  n = pm_wave_sum(n);
+  n = rsp_wave_sum_i(n);
   if ((t & 63) == 0) si[t >> 6] = n;
   __syncthreads();
   if (t == 0) rank_out[r] = v0 == v0 ? si[0] + si[1] + si[2] + si[3] : PM_MISS;
@@ -66,7 +60,7 @@ __global__ __launch_bounds__(64) void pretext_finish_kernel(const int* __restric
     h[4] += lposM[b] >= lnegM[b] ? 1 : 0;      // top-1 of cat(l_pos_M, l_neg_M) with the tie to column 0; a NaN is a miss
   }
 #pragma unroll
-  for (int i = 0; i < 5; ++i) h[i] = pm_wave_sum(h[i]);
+  for (int i = 0; i < 5; ++i) h[i] = rsp_wave_sum_i(h[i]);
   if (lane != 0) return;
   // correct_k * (100.0 / batch_size): the factor is rounded to fp32 first, as a Python scalar times a float tensor is
   const float per = (float)(100.0 / (double)B);

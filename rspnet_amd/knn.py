@@ -4,7 +4,7 @@ project's own (the reference has no such monitor); the rule is the one MoCo-styl
 Features of a labelled bank and of a labelled query set come from the backbone in eval mode (``extract``); every query's k cosine
 neighbours in the bank vote for their class with weight ``exp(s / T)``; top-1 / top-5 accuracy of the queries' own labels is the
 result.  On the HIP backend the search, the vote, the rank of the target and the hit counts are ONE call (rsp_knn_classify,
-csrc/knn.hip): the Nq x Ng similarity matrix is never stored.
+csrc/cos_search.hip, csrc/knn.hip): the Nq x Ng similarity matrix is never stored.
 
 The rule (include/rspnet_hip.h states it for the kernel; ``knn_reference`` restates it in numpy fp64):
 

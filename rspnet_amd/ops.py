@@ -159,6 +159,18 @@ def _chk(t: torch.Tensor, name: str, dtype=torch.float32):
     return t
 
 
+def _search_operands(who: str, q: torch.Tensor, g: torch.Tensor):
+    """The checks the cosine search's callers make on the query and gallery matrices; (Nq, Ng, D, row pitch of q, row pitch of g)."""
+    for n, t in (("q", q), ("g", g)):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise _lib.RspError(f"{who}: {n} must be a float32 HIP device matrix with unit column stride")
+    Nq, D = q.shape
+    Ng = g.shape[0]
+    if g.shape[1] != D:
+        raise _lib.RspError(f"{who}: feature dims differ ({D} vs {g.shape[1]})")
+    return Nq, Ng, D, q.stride(0) if Nq > 1 else D, g.stride(0) if Ng > 1 else D
+
+
 def _rows_ld(t: torch.Tensor, name: str) -> int:
     """Channel pitch of an NDHWC tensor that is either contiguous or a channel slice of a contiguous one."""
     if not t.is_cuda or t.dtype != torch.float32:
@@ -787,25 +799,18 @@ class HipOps:
                    "rsp_logits_bwd")
         return dqA, dqM
 
-    # ---- retrieval search (retrieval.hip) ------------------------------------------------------------------------
+    # ---- retrieval search (cos_search.hip, retrieval.hip) --------------------------------------------------------
     def cosine_topk(self, q, g, k: int, splits: int = 0):
         """The k nearest rows of g (Ng, D) for every row of q (Nq, D) by cosine distance: (idx int32 (Nq, k), dist fp32 (Nq, k)),
         best first; ties go to the lower gallery index; idx -1 / dist +inf past Ng.  Rows may be strided (unit column stride,
         even row pitch).  splits: gallery split count (0: automatic); the result does not depend on it."""
-        for n, t in (("q", q), ("g", g)):
-            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
-                raise _lib.RspError(f"cosine_topk: {n} must be a float32 HIP device matrix with unit column stride")
-        Nq, D = q.shape
-        Ng = g.shape[0]
-        if g.shape[1] != D:
-            raise _lib.RspError(f"cosine_topk: feature dims differ ({D} vs {g.shape[1]})")
+        Nq, Ng, D, ldq, ldg = _search_operands("cosine_topk", q, g)
         idx = torch.empty((Nq, k), dtype=torch.int32, device=q.device)
         dist = torch.empty((Nq, k), dtype=torch.float32, device=q.device)
         wsb = self.lib.rsp_cosine_topk_workspace(Nq, Ng, D, k, int(splits))
         ws = self._workspace(q.device, wsb)
-        _lib.check(self.lib.rsp_cosine_topk(_ptr(q), q.stride(0) if Nq > 1 else D, Nq, _ptr(g), g.stride(0) if Ng > 1 else D, Ng, D,
-                                            int(k), int(splits), _ptr(idx), _ptr(dist), _ptr(ws), wsb, _stream()),
-                   "rsp_cosine_topk")
+        _lib.check(self.lib.rsp_cosine_topk(_ptr(q), ldq, Nq, _ptr(g), ldg, Ng, D, int(k), int(splits), _ptr(idx), _ptr(dist), _ptr(ws),
+                                            wsb, _stream()), "rsp_cosine_topk")
         return idx, dist
 
     def topk_hits(self, idx, y_q, y_g, ks):
@@ -819,7 +824,7 @@ class HipOps:
                                           len(ks), _ptr(counts), _stream()), "rsp_topk_hits")
         return counts
 
-    # ---- weighted kNN classifier (knn.hip) -------------------------------------------------------------------------
+    # ---- weighted kNN classifier (cos_search.hip, knn.hip) ---------------------------------------------------------
     def knn_classify(self, q, g, y_g, k: int, T: float, num_classes: int, y_q=None, valid: Optional[int] = None, splits: int = 0,
                      want_idx: bool = False, want_votes: bool = False):
         """The k (1..256) cosine neighbours in g (Ng, D) of every row of q (Nq, D) vote for their class y_g with weight
@@ -828,13 +833,7 @@ class HipOps:
         (Nq, k) | None, dist fp32 (Nq, k) | None).  rank -- #classes that beat the query's own, ties to the lower class -- and hits
         -- rows i < valid with rank < 1 and rank < 5 -- come with y_q; votes / idx and dist when asked for.  Rows of q and g may be
         strided (unit column stride, even row pitch)."""
-        for n, t in (("q", q), ("g", g)):
-            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
-                raise _lib.RspError(f"knn_classify: {n} must be a float32 HIP device matrix with unit column stride")
-        Nq, D = q.shape
-        Ng = g.shape[0]
-        if g.shape[1] != D:
-            raise _lib.RspError(f"knn_classify: feature dims differ ({D} vs {g.shape[1]})")
+        Nq, Ng, D, ldq, ldg = _search_operands("knn_classify", q, g)
         _chk(y_g, "y_g", torch.int64)
         if y_g.numel() != Ng:
             raise _lib.RspError(f"knn_classify: {Ng} gallery rows, {y_g.numel()} labels")
@@ -854,10 +853,9 @@ class HipOps:
         dist = torch.empty((Nq, k), dtype=torch.float32, device=dev) if want_idx and shaped else None
         wsb = int(self.lib.rsp_knn_classify_workspace(Nq, Ng, D, k, num_classes, int(splits))) if shaped else 0
         ws = self._workspace(dev, wsb)
-        _lib.check(self.lib.rsp_knn_classify(_ptr(q), q.stride(0) if Nq > 1 else D, Nq, _ptr(y_q), _ptr(g), g.stride(0) if Ng > 1 else D,
-                                             Ng, _ptr(y_g), D, k, float(T), num_classes, int(splits), Nq if valid is None else int(valid),
-                                             _ptr(idx), _ptr(dist), _ptr(votes), _ptr(pred), _ptr(rank), _ptr(hits), _ptr(ws), wsb,
-                                             _stream()), "rsp_knn_classify")
+        _lib.check(self.lib.rsp_knn_classify(_ptr(q), ldq, Nq, _ptr(y_q), _ptr(g), ldg, Ng, _ptr(y_g), D, k, float(T), num_classes,
+                                             int(splits), Nq if valid is None else int(valid), _ptr(idx), _ptr(dist), _ptr(votes),
+                                             _ptr(pred), _ptr(rank), _ptr(hits), _ptr(ws), wsb, _stream()), "rsp_knn_classify")
         return KnnResult(pred, rank, hits, votes, idx, dist)
 
     # ---- fine-tune criterion, accuracy and meters (classify.hip) -------------------------------------------------

@@ -53,15 +53,42 @@ def test_knn_matches_fp64_reference(case):
     assert swapped <= 0.5 * total
 
 
-@pytest.mark.parametrize("k", [1, 20, 64])
-def test_neighbours_equal_the_retrieval_search_bit_for_bit(k):
-    case = CASES[5]
-    q, yq, g, yg = dev(*case_inputs(case))
+def planted_search_inputs(Nq, Ng, D, copies_of_row_5):
+    rng = np.random.default_rng(14)
+    q = rng.standard_normal((Nq, D)).astype(np.float32)
+    g = rng.standard_normal((Ng, D)).astype(np.float32)
+    if copies_of_row_5:
+        g[list(copies_of_row_5)] = g[5]
+        q[0], q[1] = g[5], 2.0 * g[5]                       # two queries whose best neighbours are the tied rows
+    return q, g, rng.integers(0, 4, Ng)
+
+
+# k alone: the seeded case 5.  (Nq, Ng, D, k, splits, copies of gallery row 5): the two places where the callers of the one S = 1 search
+# could still differ -- Ng < k (the tail is -1 / +inf through both stores, D off the 32-wide chunk), and ties that straddle the tile
+# boundary (rows 127 | 128) and the boundary of the two splits, merged by both callers.
+@pytest.mark.parametrize("k, planted", [pytest.param(1, None, id="1"), pytest.param(20, None, id="20"), pytest.param(64, None, id="64"),
+                                        pytest.param(64, (9, 40, 66, 0, ()), id="short_gallery"),
+                                        pytest.param(20, (70, 300, 130, 2, (127, 128, 200)), id="ties_on_tile_and_split_boundary")])
+def test_neighbours_equal_the_retrieval_search_bit_for_bit(k, planted):
+    if planted is None:
+        case, splits = CASES[5], 0
+        q, yq, g, yg = dev(*case_inputs(case))
+        C = case[3]
+    else:
+        Nq, Ng, D, splits, copies = planted
+        q, g, yg = dev(*planted_search_inputs(Nq, Ng, D, copies))
+        C = 4
     be = ops.backend()
-    idx, dist = be.cosine_topk(q, g, k)
-    res = be.knn_classify(q, g, yg, k, 0.07, case[3], want_idx=True)
+    idx, dist = be.cosine_topk(q, g, k, splits=splits)
+    res = be.knn_classify(q, g, yg, k, 0.07, C, want_idx=True, splits=splits)
     assert res.rank is None and res.hits is None and res.votes is None
     assert torch.equal(res.idx, idx) and torch.equal(bits(res.dist), bits(dist))
+    if planted is not None:
+        row = res.idx[0].cpu().tolist()
+        if copies:
+            assert row[:4] == [5, 127, 128, 200] and res.idx[1].cpu().tolist()[:4] == row[:4]      # the ties, lower index first
+        else:
+            assert sorted(row[:Ng]) == list(range(Ng)) and row[Ng:] == [-1] * (k - Ng) and bool(torch.isinf(res.dist[0, Ng:]).all())
 
 
 @pytest.mark.parametrize("k", [3, 200])
