@@ -632,6 +632,39 @@ size_t rsp_fingerprint_workspace(int64_t total_chunks);
 int rsp_fingerprint(const rsp_fingerprint_job* jobs_dev, int32_t n_jobs, int64_t total_chunks, rsp_fingerprint_rec* out_dev,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Label-free representation statistics (repr_stats.hip; the project's own, no counterpart in the reference): whether N embedding
+ * rows spread over the sphere or collapse, from ONE call -- the pair sums behind uniformity (Wang & Isola) and the mean pairwise cosine,
+ * the Gram matrix behind the effective rank (RankMe) and the per-dimension spread.  The N x N matrix is never stored.  Additive: the
+ * ABI version stays 130.
+ * x: N x D fp32 row-major with row pitch ld; D and ld even, ld >= D, the base 8-byte aligned; 1 <= N <= 262144, 2 <= D <= 4096.
+ * c = 2 t of the uniformity's exp(-t |xi - xj|^2) = exp(c (s - 1)): finite, in (0, 64].  gram [D][D] and colsum [D] (fp64): both or
+ * both NULL.  sums, gram, colsum and the workspace (rsp_repr_stats_workspace bytes) are 8-byte aligned.
+ *   validity    ss_i = the fp32 sum of squares of row i (each lane of a wave: its float2 columns 2 l, 2 l + 128, ... by fmaf, x then y;
+ *               then the wave's xor butterfly -- the search's inverse-norm kernel).  Row i is valid iff ss_i is finite and > 0: a zero
+ *               row and a row holding a NaN or an Inf are invalid.  An invalid row takes part in nothing and is counted in rows_bad;
+ *               its elements are selected away when staged, never multiplied by zero.  M = rows_valid.
+ *   similarity  s_ij = (x_i . x_j) * inv_i * inv_j in fp32, inv_i = 1 / sqrtf(ss_i): the search's expression.
+ *   pair sums   over valid i < j, each pair exactly once: pair_exp = sum expf(c * (s - 1)) (the argument is <= about 0: nothing
+ *               overflows), pair_cos = sum s, pair_cos2 = sum s * s.  Each thread adds its 32 elements of a 64 x 128 tile in fp32 in a
+ *               fixed order; everything above that -- a thread's tiles, the workgroup, the partials in the workspace, the final
+ *               reduce -- is added in fp64 in a fixed order: the same input and the same N give the same bits.
+ *   gram        gram[a][b] = sum over valid i of xh_ia * xh_ib, colsum[a] = sum over valid i of xh_ia, xh = x * inv formed in fp32 when
+ *               staged.  Products and the accumulation inside a split of the row axis run on the fp32 MFMA (colsum: fp32 adds in row
+ *               order); the split count is chosen from N and D; the splits are added in fp64 in split order.  Every element of gram
+ *               is written, both triangles; a 64 x 128 tile wholly below the diagonal is the mirror image of the computed elements
+ *               above it, so gram is symmetric to the bit.
+ * A bad argument is RSP_EINVAL, a workspace below the query RSP_EWORKSPACE, both before anything is launched.  Kernels only, all on
+ * `stream`: no memset, no memcpy, no atomics; capturable after a first eager call.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct rsp_repr_sums {      /* device struct, 40 bytes */
+  double pair_exp, pair_cos, pair_cos2;   /* sums over valid pairs i < j of exp(c*(s-1)), s, s*s */
+  int64_t rows_valid, rows_bad;
+} rsp_repr_sums;
+size_t rsp_repr_stats_workspace(int32_t N, int32_t D);
+int rsp_repr_stats(const float* x, int32_t ld, int32_t N, int32_t D, float c, rsp_repr_sums* sums, double* gram, double* colsum,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

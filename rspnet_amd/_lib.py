@@ -74,6 +74,12 @@ class FingerprintRec(C.Structure):
                 ("nonfinite", C.c_uint32)]
 
 
+class ReprSums(C.Structure):
+    """rsp_repr_sums (40 bytes)"""
+    _fields_ = [("pair_exp", C.c_double), ("pair_cos", C.c_double), ("pair_cos2", C.c_double), ("rows_valid", C.c_int64),
+                ("rows_bad", C.c_int64)]
+
+
 _PD = C.POINTER(ConvDesc)
 _PP = C.POINTER(PoolDesc)
 _sz = C.c_size_t
@@ -174,6 +180,8 @@ SIGNATURES = {
     "rsp_cam_overlay": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "rsp_fingerprint_workspace": (_sz, [_i64]),
     "rsp_fingerprint": (C.c_int, [_p, _i32, _i64, _p, _p, _sz, _p]),
+    "rsp_repr_stats_workspace": (_sz, [_i32, _i32]),
+    "rsp_repr_stats": (C.c_int, [_p, _i32, _i32, _i32, _f, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

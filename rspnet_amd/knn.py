@@ -192,8 +192,9 @@ class KNNMonitor:
                                            n_crop=self.n_crop, seed=seed)
         return bank, query
 
-    def run(self, model: nn.Module, bank_loader: Iterable, query_loader: Iterable) -> dict:
-        """{"acc1", "acc5", "n_bank", "n_query", "seconds"}.  ``model``: the pretext model (or its wrapper with ``.module``)."""
+    def run(self, model: nn.Module, bank_loader: Iterable, query_loader: Iterable, return_features: bool = False) -> dict:
+        """{"acc1", "acc5", "n_bank", "n_query", "seconds"}, with ``return_features`` also "bank_features": the (n_bank, D) backbone
+        features it extracted, on the device.  ``model``: the pretext model (or its wrapper with ``.module``)."""
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("KNNMonitor.run: never inside a graph capture")
         net = getattr(model, "module", model)
@@ -216,8 +217,11 @@ class KNNMonitor:
                 m.training = was
         valid = query_loader.num_valid_samples() if hasattr(query_loader, "num_valid_samples") else q.shape[0]
         res = knn_classify(q, y_q, g, y_g, self.k, self.t, self.num_classes, valid=min(int(valid), q.shape[0]))
-        return {"acc1": res["acc1"], "acc5": res["acc5"], "n_bank": int(g.shape[0]), "n_query": res["n"],
-                "seconds": time.perf_counter() - t0}
+        out = {"acc1": res["acc1"], "acc5": res["acc5"], "n_bank": int(g.shape[0]), "n_query": res["n"],
+               "seconds": time.perf_counter() - t0}
+        if return_features:
+            out["bank_features"] = g
+        return out
 
 
 # ---- command line over saved retrieval features --------------------------------------------------------------------------

@@ -200,6 +200,7 @@ def _dy_target(y, in_ld: int, dy_out):
 
 
 KnnResult = collections.namedtuple("KnnResult", "pred rank hits votes idx dist")      # of HipOps.knn_classify
+ReprResult = collections.namedtuple("ReprResult", "sums gram colsum")                  # of HipOps.repr_stats
 
 
 class HipOps:
@@ -857,6 +858,26 @@ class HipOps:
                                              int(splits), Nq if valid is None else int(valid), _ptr(idx), _ptr(dist), _ptr(votes),
                                              _ptr(pred), _ptr(rank), _ptr(hits), _ptr(ws), wsb, _stream()), "rsp_knn_classify")
         return KnnResult(pred, rank, hits, votes, idx, dist)
+
+    # ---- label-free representation statistics (repr_stats.hip) ------------------------------------------------------
+    def repr_stats(self, x, t: float = 2.0, want_gram: bool = True):
+        """The pair sums, the Gram matrix and the column sums of the rows of x (N, D) from one rsp_repr_stats call (the N x N matrix
+        never stored; include/rspnet_hip.h states the rule).  Returns the named tuple (sums: the 40-byte rsp_repr_sums as a uint8
+        device tensor -- pair sums of exp(2 t (s - 1)), s, s^2 over the valid pairs i < j, then the valid and invalid row counts --,
+        gram fp64 (D, D) | None, colsum fp64 (D,) | None).  Rows may be strided (unit column stride, even row pitch)."""
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+            raise _lib.RspError("repr_stats: x must be a float32 HIP device matrix with unit column stride")
+        N, D = x.shape
+        ld, dev = x.stride(0) if N > 1 else D, x.device
+        sums = torch.empty(C.sizeof(_lib.ReprSums), dtype=torch.uint8, device=dev)
+        shaped = want_gram and 2 <= D <= 4096          # (the call itself rejects the rest, before any launch)
+        gram = torch.empty((D, D), dtype=torch.float64, device=dev) if shaped else None
+        colsum = torch.empty(D, dtype=torch.float64, device=dev) if shaped else None
+        wsb = int(self.lib.rsp_repr_stats_workspace(N, D))
+        ws = self._workspace(dev, wsb)
+        _lib.check(self.lib.rsp_repr_stats(_ptr(x), ld, N, D, 2.0 * float(t), _ptr(sums), _ptr(gram), _ptr(colsum), _ptr(ws), wsb,
+                                           _stream()), "rsp_repr_stats")
+        return ReprResult(sums, gram, colsum)
 
     # ---- fine-tune criterion, accuracy and meters (classify.hip) -------------------------------------------------
     def xent_metrics(self, logits, target, n_crop: int = 1, valid: Optional[int] = None, want_grad: bool = True, meters=None):

@@ -22,7 +22,7 @@ from pathlib import Path
 
 import torch
 
-from . import _lib, fingerprint, knn, ops
+from . import _lib, fingerprint, knn, ops, repr_stats
 from .framework.arguments import RUN_DIR_NAME_REGEX, add_driver_arguments, parse_driver_args, save_run_files  # noqa: F401
 from .framework.driver import (append_scalars, finish_process_group, init_process_group, launch, load_config, load_states, save_run,
                                seed_everything, setup_logging, visible_gpu_count)
@@ -181,6 +181,10 @@ class Engine:
         self.knn_loaders, self._knn_result = knn_loaders, None
         if self.knn is not None and knn_loaders is None and local_rank == 0:
             self.knn_loaders = self.knn.build_loaders(T, size, self.device, seed=args.seed)
+        # opt-in (config key "repr_monitor", e.g. -x '{"repr_monitor": {"every": 10, "t": 2.0}}'): None otherwise.  Rank 0 reads the
+        # queue (rank-identical by construction); no labels, no loaders
+        self.repr_monitor = repr_stats.ReprMonitor.from_config(cfg, self.num_epochs)
+        self._repr_result, self._bank_features = None, None
 
     # ---- checkpoints (pretrain.py:112-132) ---------------------------------------------------------------------------
     def load_checkpoint(self, path):
@@ -267,6 +271,8 @@ class Engine:
         rec.update({f"train/{k}": self.stats[k]["avg"] for k in ("loss", "loss_A", "acc1_A", "acc5_A", "loss_M", "acc1_M")})
         if self._knn_result is not None:
             rec.update({"knn/acc1": self._knn_result["acc1"], "knn/acc5": self._knn_result["acc5"]})
+        if self._repr_result is not None:
+            rec.update(self._repr_result)
         append_scalars(self.scalars_path, rec)
 
     def _run_knn_monitor(self):
@@ -277,9 +283,36 @@ class Engine:
         if m is None or not m.due(self.current_epoch):
             return
         if self.local_rank == 0:
-            r = self._knn_result = m.run(self.model, *self.knn_loaders)
+            # with the representation monitor due as well, the bank's backbone features go through it too
+            want_bank = self.repr_monitor is not None and self.repr_monitor.due(self.current_epoch)
+            r = self._knn_result = m.run(self.model, *self.knn_loaders, **({"return_features": True} if want_bank else {}))
+            self._bank_features = r.pop("bank_features", None)
             logger.info(f"kNN [{self.current_epoch}/{self.num_epochs}]\tAcc@1 {r['acc1']:.2f}\tAcc@5 {r['acc5']:.2f}"
                         f"\t(k={m.k}, T={m.t}, bank {r['n_bank']}, query {r['n_query']}, {r['seconds']:.1f} s)")
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            torch.distributed.barrier()
+
+    def _run_repr_monitor(self):
+        """After the kNN monitor and before the epoch's scalar line: rank 0 computes the label-free statistics of the queue -- and of
+        the bank features when the kNN monitor has just extracted them -- eagerly on the current stream; the other ranks wait at a
+        barrier.  Has run on one GPU only."""
+        self._repr_result = None
+        bank, self._bank_features = self._bank_features, None
+        m = self.repr_monitor
+        if m is None or not m.due(self.current_epoch):
+            return
+        if self.local_rank == 0:
+            r = m.run(self.model)
+            rec = {f"repr/{k}": r[k] for k in ("uniformity", "mean_cos", "effective_rank", "dim_std_min", "bad_rows")}
+            line = (f"Repr [{self.current_epoch}/{self.num_epochs}]\tuniformity {r['uniformity']:.4f}\teff.rank "
+                    f"{r['effective_rank']:.1f}/{self.model.module.queue.shape[0]}\tmean cos {r['mean_cos']:.4f}\tdim std min "
+                    f"{r['dim_std_min']:.3f}\t(t={m.t}, {r['rows']} rows, {r['bad_rows']} bad, {r['seconds']:.2f} s)")
+            if bank is not None:
+                b = repr_stats.repr_stats(bank, m.t)
+                rec.update({f"repr/bank_{k}": b[k] for k in ("uniformity", "effective_rank", "dim_std_min")})
+                line += f"\tbank: uniformity {b['uniformity']:.4f}\teff.rank {b['effective_rank']:.1f}/{bank.shape[1]}"
+            self._repr_result = rec
+            logger.info(line)
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             torch.distributed.barrier()
 
@@ -298,6 +331,7 @@ class Engine:
             lr = float(self.optimizer.param_groups[0]["lr"])
             stats = self.train_epoch()
             self._run_knn_monitor()
+            self._run_repr_monitor()
             self.scheduler.step()
             self._write_scalars(lr)
             self.current_epoch += 1
