@@ -463,6 +463,18 @@ int rsp_augment_batch(const rsp_augment_clip_desc* descs, int32_t n_clips, int32
  * gallery index.  A zero-norm row has similarity 0 (distance 1) to everything.  When Ng < k the tail slots hold index -1 and
  * distance +inf.  The Nq x Ng matrix is never stored.  splits: gallery ranges searched by separate workgroups and merged
  * (<= 0: chosen from the sizes; rsp_cosine_topk_splits tells the count used); the output does not depend on it, bit for bit.
+ *
+ * Non-finite rows (the same for rsp_knn_classify, any k, any split count).  The inverse norm of a row is 1 / sqrt(sum of squares) in
+ * fp32 where that sum is positive and finite, and 0 otherwise: for a zero row, for a row holding a NaN or an Inf, and for a finite row
+ * whose squares overflow fp32 (an element beyond about 1.8e19).  The similarity is (q.g) * (1/|q|) * (1/|g|) as always, so
+ *   - a gallery row holding a NaN or an Inf has a NaN similarity to every query (NaN or +-inf times 0).  A NaN similarity never
+ *     enters a list: such a row is never returned, and every other row is ranked exactly as if the gallery did not hold it -- the
+ *     lists equal, bit for bit, those of a search without these rows (indices shifted).  With fewer than k rows left the tail is -1
+ *     / +inf, as for Ng < k;
+ *   - a query row holding a NaN or an Inf has a NaN similarity to every gallery row: index -1 and distance +inf in all k slots;
+ *   - a finite row whose squares overflow behaves as a zero row -- similarity 0, distance 1 -- as long as its fp32 dot products stay
+ *     finite; a dot product that overflows too gives NaN (inf * 0) and that pair is left out.  (torch.topk would rank a NaN first;
+ *     sklearn's cosine_distances, which the reference calls, refuses non-finite input.)
  * ------------------------------------------------------------------------------------------------------------- */
 int32_t rsp_cosine_topk_splits(int32_t Nq, int32_t Ng, int32_t splits);
 size_t rsp_cosine_topk_workspace(int32_t Nq, int32_t Ng, int32_t D, int32_t k, int32_t splits);
@@ -470,7 +482,9 @@ int rsp_cosine_topk(const float* q, int32_t ldq, int32_t Nq, const float* g, int
                     int32_t splits, int32_t* idx, float* dist, void* workspace, size_t workspace_bytes, void* stream);
 /* counts[i] = number of queries whose label y_q[row] appears among the labels y_g[idx[row][0 .. ks[i])] (retrieval.py:169-
  * 176).  idx: the Nq x k output of rsp_cosine_topk (negative entries never hit); y_q / y_g: int64 device labels; ks_host: HOST
- * array of nks (1..16) values in [1, k], read during the call; counts: nks int32 on the device. */
+ * array of nks (1..16) values in [1, k], read during the call; counts: nks int32 on the device.  A query whose row held a NaN or an
+ * Inf comes out of the search with -1 in every slot, so it is counted for no k (it stays in the denominator Nq the caller divides
+ * by); a gallery row holding one is in no list and so hits for nobody. */
 int rsp_topk_hits(const int32_t* idx, int32_t Nq, int32_t k, const int64_t* y_q, const int64_t* y_g, int32_t Ng,
                   const int32_t* ks_host, int32_t nks, int32_t* counts, void* stream);
 
@@ -494,6 +508,12 @@ int rsp_topk_hits(const int32_t* idx, int32_t Nq, int32_t k, const int64_t* y_q,
  *               of rsp_xent_metrics); num_classes -- a miss -- for a y_q[i] outside [0, num_classes).
  *   hits        [2] (may be NULL; needs y_q): the number of i < valid with rank[i] < 1 and with rank[i] < 5 (also written when
  *               num_classes < 5).  0 <= valid <= Nq cuts the repeated tail of a wrapped last batch.
+ *   non-finite  rows: the search's rule (above).  A gallery row holding a NaN or an Inf is nobody's neighbour and casts no vote; the
+ *               other rows vote exactly as if the gallery did not hold it.  A query row holding one has no neighbours: idx -1 and
+ *               dist +inf in every slot, every vote 0, pred 0 (all classes tie, the lower wins) and rank = y_q[i] (the classes
+ *               below the label stand ahead of it in that tie), so hits[0] counts it only if its label is 0 and hits[1] only if its
+ *               label is below 5 -- what a constant prediction of class 0 would score.  A finite row whose squares overflow votes
+ *               and is voted for as a zero row: similarity 0, weight exp(-1 / T).
  * A bad argument is RSP_EINVAL, a workspace below rsp_knn_classify_workspace RSP_EWORKSPACE, before anything is launched.
  * Kernels only, all on `stream`.
  * ------------------------------------------------------------------------------------------------------------- */
@@ -519,7 +539,11 @@ int rsp_knn_classify(const float* q, int32_t ldq, int32_t Nq, const int64_t* y_q
  *   meters                   device struct, may be NULL: val[i] = v_i, sum[i] += v_i * valid, count[i] += valid for (loss, acc1, acc5).
  * classes < 5: acc[1] and the acc5 meter are left untouched (:137-139).  valid == 0: only avg_logits, loss and dlogits are written
  * (:121-122).  A target outside [0, classes) or a NaN logit makes that sample's loss (and so `loss`) NaN and the sample a miss; the
- * gradient rows of a sample with a bad target are NaN.  No atomics: the same input gives the same bits.
+ * gradient rows of a sample with a bad target are NaN.  Infinite logits follow nn.CrossEntropyLoss and torch.topk: -inf off the
+ * target contributes nothing; -inf at the target gives that sample the loss +inf, a finite gradient and the last rank; +inf
+ * anywhere in a row (or a row of -inf only) makes the sample's loss and its gradient rows NaN (inf - inf), while its rank is still
+ * the count above -- +inf at the target is a hit, +inf elsewhere stands ahead of the target.  (n_crop > 1: the rule applies to the
+ * crop mean, which is NaN when the crops hold +inf and -inf.)  No atomics: the same input gives the same bits.
  * ------------------------------------------------------------------------------------------------------------- */
 typedef struct rsp_cls_meters {   /* order: loss, acc1, acc5 */
   float val[3];

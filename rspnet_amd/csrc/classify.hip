@@ -4,8 +4,9 @@
 //
 // Rank rule: rank(s) = #{c : avg[s][c] > avg[s][t]} + #{c < t : avg[s][c] == avg[s][t]}, t = target[s]; top-1 needs rank 0, top-5
 // rank < 5.  An exact tie therefore goes to the lower class index (torch.topk leaves ties unspecified: the one divergence).  A
-// sample whose loss is NaN (NaN logit, target outside [0, classes)) is a miss, and the rows of a sample with a bad target get
-// a NaN gradient: the batch loss is NaN then, and its gradient must not look usable.
+// sample with a NaN (crop-mean) logit or a target outside [0, classes) is a miss, and the rows of a sample with a bad target get
+// a NaN gradient: the batch loss is NaN then, and its gradient must not look usable.  Infinite logits are ranked by the comparison
+// like any other value (torch.topk's accuracy): +inf at the target is a hit although the sample's loss is NaN.
 //
 // Kernels (no atomics, no fences, fixed reduction order: the same input gives the same bits):
 //   xent_sample_kernel   one workgroup of 256 per sample, thread t owns classes t, t + 256, ... (at most 16: classes <= 4096) in
@@ -37,7 +38,7 @@ __global__ __launch_bounds__(XE_THREADS) void xent_sample_kernel(const float* __
                                                                  float* __restrict__ avg_logits, float* __restrict__ dlogits,
                                                                  float* __restrict__ sample_loss, int* __restrict__ sample_rank) {
   __shared__ float sf[2][XE_THREADS / 64];
-  __shared__ int si[XE_THREADS / 64];
+  __shared__ int si[2][XE_THREADS / 64];
   const int s = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const float* base = logits + (long long)s * n_crop * ld;
   const long long tg = target[s];
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(XE_THREADS) void xent_sample_kernel(const float* __
   const float vt = good ? crop_mean(base, ld, n_crop, (int)tg) : 0.f;
   float e[XE_PER];
   float sum = 0.f;
-  int rank = 0;
+  int rank = 0, nans = 0;
 #pragma unroll
   for (int i = 0; i < XE_PER; ++i) {
     const int c = t + XE_THREADS * i;
@@ -72,22 +73,28 @@ __global__ __launch_bounds__(XE_THREADS) void xent_sample_kernel(const float* __
       e[i] = expf(v[i] - m);
       sum += e[i];
       rank += (v[i] > vt || (v[i] == vt && c < (int)tg)) ? 1 : 0;
+      nans += v[i] != v[i] ? 1 : 0;
     }
   }
   sum = rsp_wave_sum(sum);
   rank = rsp_wave_sum_i(rank);
+  nans = rsp_wave_sum_i(nans);
   if (lane == 0) {
     sf[1][wave] = sum;
-    si[wave] = rank;
+    si[0][wave] = rank;
+    si[1][wave] = nans;
   }
   __syncthreads();
   sum = ((sf[1][0] + sf[1][1]) + sf[1][2]) + sf[1][3];
-  rank = si[0] + si[1] + si[2] + si[3];
+  rank = si[0][0] + si[0][1] + si[0][2] + si[0][3];
+  nans = si[1][0] + si[1][1] + si[1][2] + si[1][3];
 
   const float loss = good ? (logf(sum) + m) - vt : NAN;
   if (t == 0) {
     sample_loss[s] = loss;
-    sample_rank[s] = loss == loss ? rank : XE_MISS;      // a NaN loss (NaN logit, bad target) is a miss
+    // a NaN logit or a bad target is a miss; an infinite logit is ranked by comparison like any other value, as torch.topk ranks
+    // it, though +inf anywhere in the row makes the loss NaN (inf - inf)
+    sample_rank[s] = good && nans == 0 ? rank : XE_MISS;
   }
   if (dlogits) {
     const float denom = (float)S * (float)n_crop;

@@ -11,7 +11,10 @@ nobody wrote still holds the word 0xFFFFFFFF (a NaN no arithmetic produces; int3
 into the result, where the test's own comparison fails on it.  Nothing here can fault: every such access stays inside the block.
 
 The payload pointer is 16-byte aligned and not 32-byte aligned (skew=16, the conv / BatchNorm family's contract); skew=8 gives the
-search kernels' 8-byte alignment.  Not a conftest, no pytest settings: a helper the guarded tests import."""
+search kernels' 8-byte alignment, skew=4 the 4-byte alignment of the kernels that promise a float pointer and no more (an element
+of 8 bytes and a byte buffer the op allocates itself still start on 8: what the allocator and the header give them).  ops_module may be a list: every module
+named has its `torch` replaced (rspnet_amd.fingerprint allocates its table and records itself; rspnet_amd.ops the workspace).
+Not a conftest, no pytest settings: a helper the guarded tests import."""
 import os
 import sys
 
@@ -27,7 +30,7 @@ class GuardError(AssertionError):
 
 
 class _Block:
-    __slots__ = ("name", "block", "band", "nbytes", "payload", "kind", "bits", "proxy", "dtype")
+    __slots__ = ("name", "block", "band", "nbytes", "payload", "kind", "bits", "proxy", "dtype", "partial")
 
 
 class _TorchProxy:
@@ -69,22 +72,27 @@ class _TorchProxy:
 class Guarded:
     def __init__(self, device, skew=16, hip=None, ops_module=None):
         """hip: the backend whose workspace is guarded (default: rspnet_amd.ops.backend() on a HIP device, none on the CPU);
-        ops_module: the module whose `torch` is replaced (default: rspnet_amd.ops)."""
+        ops_module: the module, or the list of modules, whose `torch` is replaced (default: rspnet_amd.ops)."""
         self.device = torch.device(device)
-        assert skew in (8, 16), skew
+        assert skew in (4, 8, 16), skew
         self.skew = skew
         self.blocks = []
         if ops_module is None:
             from rspnet_amd import ops as ops_module
-        self._ops = ops_module
-        self._hip = hip if hip is not None else (ops_module.backend() if self.device.type == "cuda" else None)
+        self._modules = list(ops_module) if isinstance(ops_module, (list, tuple)) else [ops_module]
+        if hip is None and self.device.type == "cuda":
+            from rspnet_amd import ops
+            hip = ops.backend()
+        self._hip = hip
 
     # ---- activation ---------------------------------------------------------------------------------------------------
     def __enter__(self):
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("Guarded: refusing to activate while a stream is capturing")
-        self._saved_torch = self._ops.torch
-        self._ops.torch = _TorchProxy(self)
+        self._saved_torch = [m.torch for m in self._modules]
+        proxy = _TorchProxy(self)
+        for m in self._modules:
+            m.torch = proxy
         hip = self._hip
         if hip is not None:
             self._saved_ws = hip._ws
@@ -101,7 +109,8 @@ class Guarded:
         return self
 
     def __exit__(self, *exc):
-        self._ops.torch = self._saved_torch
+        for m, saved in zip(self._modules, self._saved_torch):
+            m.torch = saved
         hip = self._hip
         if hip is not None:
             hip._ws = self._saved_ws
@@ -136,17 +145,32 @@ class Guarded:
         for s in shape:
             numel *= s
         nbytes = numel * itemsize
-        band = (min(max(nbytes, BAND_MIN), BAND_MAX) + 63) // 64 * 64 + self.skew
-        block = torch.full((2 * band + nbytes,), FILL, dtype=torch.uint8, device=self.device)
         b = _Block()
         b.name = name or self._call_site()
+        # (a byte buffer an op allocates is a workspace, a job table or a record array: structs with 8-byte members)
+        skew = max(self.skew, 8) if itemsize > self.skew or (_proxy and dtype == torch.uint8) else self.skew
+        band = (min(max(nbytes, BAND_MIN), BAND_MAX) + 63) // 64 * 64 + skew
+        block = torch.full((2 * band + nbytes,), FILL, dtype=torch.uint8, device=self.device)
         b.block, b.band, b.nbytes = block, band, nbytes
         b.payload = block[band:band + nbytes]
         b.proxy, b.dtype = _proxy, dtype
         b.kind = "workspace" if "(_workspace)" in b.name else ("output" if _proxy else "operand")
         b.bits = None
+        b.partial = False
         self.blocks.append(b)
         return b.payload.view(dtype).view(shape)
+
+    def block_of(self, t):
+        """The block whose payload holds the first element of t."""
+        p = t.data_ptr()
+        for b in self.blocks:
+            if b.payload.data_ptr() <= p < b.payload.data_ptr() + max(b.nbytes, 1):
+                return b
+        raise KeyError("not a guarded tensor")
+
+    def allow_unwritten(self, t):
+        """An op's output that its contract leaves partly untouched (the test says which words, and looks at them itself)."""
+        self.block_of(t).partial = True
 
     def empty(self, *shape, dtype=torch.float32):
         """alloc with torch.empty's way of giving the size: empty(2, 3) or empty((2, 3))."""
@@ -180,7 +204,7 @@ class Guarded:
             probes.append((front != FILL).any())
             probes.append((back != FILL).any())
             probes.append((b.payload != b.bits).any() if b.bits is not None else torch.zeros((), dtype=torch.bool, device=self.device))
-            written = b.proxy and b.kind == "output" and b.nbytes and b.dtype == torch.float32
+            written = b.proxy and b.kind == "output" and b.nbytes and b.dtype == torch.float32 and not b.partial
             probes.append((b.payload.view(torch.int32) == -1).any() if written
                           else torch.zeros((), dtype=torch.bool, device=self.device))
         if not probes:

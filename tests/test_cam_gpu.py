@@ -24,6 +24,12 @@ FUZZ = [(1, 1, 1, 1, 24, 16, 16, 0), (1, 2, 3, 3, 83, 128, 1, 0), (3, 1, 1, 1, 1
         (4, 1, 5, 2, 83, 7, 7, 96), (7, 3, 1, 2, 512, 128, 128, 640), (2, 1, 1, 9, 24, 3, 5, 24), (9, 2, 7, 7, 64, 128, 128, 0)]
 
 
+# Where maps_case / check_maps / the overlay body place their operands on the device.  tests/test_guarded_downstream_gpu.py runs them
+# with dev() pointed at guarded allocations (tests/guarded.py).
+def dev(t):
+    return t.to(DEV)
+
+
 def maps_case(seed, B, Tp, Hp, Wp, C, dim_A=128, dim_M=128, pitch=0, identity=True):
     """Features relu(N(0, 1)), weights N(0, 1 / C); pitch > C: the features are channel slices of a wider tensor."""
     g = torch.Generator().manual_seed(seed)
@@ -33,9 +39,9 @@ def maps_case(seed, B, Tp, Hp, Wp, C, dim_A=128, dim_M=128, pitch=0, identity=Tr
         if pitch:
             wide = torch.full((B, Tp, Hp, Wp, pitch), float("nan"))
             wide[..., :C] = f
-            feats.append(wide.to(DEV)[..., :C])
+            feats.append(dev(wide)[..., :C])
         else:
-            feats.append(f.to(DEV))
+            feats.append(dev(f))
     ws = [torch.randn(d, C, generator=g) / C ** 0.5 for d in (dim_A, dim_M, dim_A, dim_M)]
     k_row = torch.arange(B) if identity else torch.randperm(B, generator=g)
     return feats, ws, k_row.to(torch.int32)
@@ -44,8 +50,9 @@ def maps_case(seed, B, Tp, Hp, Wp, C, dim_A=128, dim_M=128, pitch=0, identity=Tr
 def check_maps(seed, B, Tp, Hp, Wp, C, dim_A=128, dim_M=128, pitch=0, identity=True):
     (fq, fk), ws, k_row = maps_case(seed, B, Tp, Hp, Wp, C, dim_A, dim_M, pitch, identity)
     be = ops.backend()
-    out = be.cam_maps(fq, fk, k_row.to(DEV), *[w.to(DEV) for w in ws])
-    again = be.cam_maps(fq, fk, k_row.to(DEV), *[w.to(DEV) for w in ws])
+    kd, wd = dev(k_row), [dev(w) for w in ws]
+    out = be.cam_maps(fq, fk, kd, *wd)
+    again = be.cam_maps(fq, fk, kd, *wd)
     assert out.shape == (4, B, Tp, Hp, Wp) and out.dtype == torch.float32
     assert torch.equal(out.view(torch.int32), again.view(torch.int32))          # run-to-run bit-identical
     ncdhw = lambda x: x.cpu().permute(0, 4, 1, 2, 3)
@@ -164,15 +171,16 @@ def test_cam_overlay_matches_restatement(size, Tp):
     maps[5] = 0.25
     clip_a, clip_b = torch.rand(B, 3, T, size, size, generator=g), torch.rand(B, 3, T, size, size, generator=g)
     be = ops.backend()
-    out = be.cam_overlay(maps.to(DEV), clip_a.to(DEV), clip_b.to(DEV), t)
+    md, ad, bd = dev(maps), dev(clip_a), dev(clip_b)
+    out = be.cam_overlay(md, ad, bd, t)
     assert out.shape == (4 * B, size, size, 3) and out.dtype == torch.uint8
-    assert torch.equal(out, be.cam_overlay(maps.to(DEV), clip_a.to(DEV), clip_b.to(DEV), t))
+    assert torch.equal(out, be.cam_overlay(md, ad, bd, t))
     want = cam_overlay_ref(maps, clip_a, clip_b, t)
     diff = (out.cpu().to(torch.int16) - want.to(torch.int16)).abs()
     print(f"cam_overlay size={size} T'={Tp}: max diff {int(diff.max())}, pixels off by one {int((diff > 0).sum())} of {diff.numel()}")
     assert int(diff.max()) <= 1
     # one clip for all panels
-    single = be.cam_overlay(maps[:B].to(DEV), clip_a.to(DEV), None, 0)
+    single = be.cam_overlay(md[:B], ad, None, 0)
     assert int((single.cpu().to(torch.int16) - cam_overlay_ref(maps[:B], clip_a, None, 0).to(torch.int16)).abs().max()) <= 1
 
 

@@ -23,6 +23,16 @@ def dev():
     return torch.device("cuda", 0)
 
 
+# Where check_case places its operands on the device.  tests/test_guarded_downstream_gpu.py runs it with these two pointed at guarded
+# allocations (tests/guarded.py): place() for inputs, place_empty() for what the kernel updates in place.
+def place(t):
+    return t.to(dev())
+
+
+def place_empty(*shape, dtype=torch.float32):
+    return torch.empty(*shape, dtype=dtype, device=dev())
+
+
 def restate(logits, n_crop, target, valid):
     """fp64 restatement of rsp_xent_metrics.  The crop mean is DEFINED in fp32 (sum in crop order, one division), so the ranks are
     taken on that fp32 mean, evaluated here with numpy's fp32 arithmetic; everything else is fp64."""
@@ -63,13 +73,14 @@ def read_meters(buf):
 
 def check_case(be, logits, n_crop, target, valid, padded=False):
     rows, classes = logits.shape
-    lt = torch.from_numpy(logits).to(dev())
     if padded:      # ld > classes: a column slice of a wider matrix
-        wide = torch.full((rows, classes + 3), float("nan"), device=dev())
-        wide[:, :classes] = lt
-        lt = wide[:, :classes]
-    meters = torch.zeros(36, dtype=torch.uint8, device=dev())
-    avg, loss, acc, dl = be.xent_metrics(lt, torch.from_numpy(target).to(dev()), n_crop=n_crop, valid=valid, meters=meters)
+        wide = torch.full((rows, classes + 3), float("nan"))
+        wide[:, :classes] = torch.from_numpy(logits)
+        lt = place(wide)[:, :classes]
+    else:
+        lt = place(torch.from_numpy(logits))
+    meters = place_empty(36, dtype=torch.uint8).zero_()
+    avg, loss, acc, dl = be.xent_metrics(lt, place(torch.from_numpy(target)), n_crop=n_crop, valid=valid, meters=meters)
     ravg, rloss, rdl, h1, h5 = restate(logits, n_crop, target, valid)
     assert l2(avg.cpu().numpy(), ravg) <= GATE
     assert abs(float(loss) - rloss) <= GATE * max(abs(rloss), 1e-30) or rloss == 0.0 == float(loss), (float(loss), rloss)

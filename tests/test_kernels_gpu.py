@@ -76,6 +76,9 @@ CONV_CASES = [
     (1, 4, 70, 80, 32, 144, (3, 3, 3), (1, 1, 1), (1, 1, 1)),      # 175 tiles, bias + statistics on every one
     (2, 4, 9, 9, 144, 140, (3, 3, 3), (2, 2, 2), (1, 1, 1)),       # dgrad classes with N = 144; forward 140 columns
     (3, 4, 7, 7, 128, 144, (3, 3, 3), (1, 1, 1), (1, 1, 1)),       # slice-major K, depth-major rows (two linear runs per tile)
+    # S3D-G's 144 -> 288 (1,3,3) at full size: the only shape whose input gradient runs the 144-wide half-block tile with the
+    # slice-major K walk (at N <= 8 the plan takes the 32-wide tile); tests/test_instance_closure_cpu.py needs it here
+    (16, 4, 14, 14, 144, 288, (1, 3, 3), (1, 1, 1), (0, 1, 1)),
     # >= 768 tiles: the single-LDS-buffer mode of the 128- / 96-wide tiles (three workgroups per CU), with a K-split tail
     (1, 6, 130, 128, 16, 128, (3, 3, 3), (1, 1, 1), (1, 1, 1)),    # 780 tiles of 128x128, K = 432
     (1, 6, 130, 128, 16, 96, (1, 3, 3), (1, 1, 1), (0, 1, 1)),     # 780 tiles of 128x96

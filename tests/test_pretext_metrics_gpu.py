@@ -27,6 +27,16 @@ def backend():
     return be
 
 
+# Where call() places its operands on the device.  tests/test_guarded_downstream_gpu.py runs the bodies with these two pointed at
+# guarded allocations (tests/guarded.py): place() for inputs, place_empty() for what the kernel writes.
+def place(t):
+    return t.to(dev())
+
+
+def place_empty(*shape, dtype=torch.float32):
+    return torch.empty(*shape, dtype=dtype, device=dev())
+
+
 def restate(l1, l2, lp, ln):
     from rspnet_amd.pretrain import pretext_accuracy
     return pretext_accuracy((l1, l2), (lp.view(-1, 1), ln.view(-1, 1)))
@@ -41,12 +51,12 @@ def ranks_of(x):
 def call(be, l1, l2, lp, ln, losses=None, meters=None):
     """The entry point itself, with a workspace of the test's own: returns (acc, ranks of the 2 * B rows) on the host."""
     B, K1 = l1.shape
-    d = [t.to(dev()).contiguous() for t in (l1, l2, lp.reshape(-1), ln.reshape(-1))]
-    ls = None if losses is None else losses.to(dev())
-    acc = torch.full((5,), -1.0, device=dev())
+    d = [place(t.contiguous()) for t in (l1, l2, lp.reshape(-1), ln.reshape(-1))]
+    ls = None if losses is None else place(losses)
+    acc = place_empty(5).fill_(-1.0)
     wsb = be.lib.rsp_pretext_metrics_workspace(B)
     assert wsb == 8 * B
-    ws = torch.full((2 * B,), -7, dtype=torch.int32, device=dev())
+    ws = place_empty(2 * B, dtype=torch.int32).fill_(-7)
     rc = be.lib.rsp_pretext_metrics(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), B, K1,
                                     None if ls is None else ls.data_ptr(), acc.data_ptr(),
                                     None if meters is None else meters.data_ptr(), ws.data_ptr(), wsb,
