@@ -689,6 +689,54 @@ size_t rsp_repr_stats_workspace(int32_t N, int32_t D);
 int rsp_repr_stats(const float* x, int32_t ld, int32_t N, int32_t D, float c, rsp_repr_sums* sums, double* gram, double* colsum,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Linear probe on frozen features (linear_probe.hip; the reference configures it as finetune's `linear` overlay, only_train_fc, and
+ * runs the frozen backbone again every epoch): a softmax classifier fitted by SGD with momentum on N stored feature rows, all
+ * `steps` steps issued from ONE call, nothing read back.  Additive: the ABI version stays 130.
+ * x: N x D fp32 row-major with row pitch ld; D and ld even, ld >= D, the base 8-byte aligned (the rule of the cosine search);
+ * y [N] int64, 8-byte aligned.  1 <= C <= 1024, 1 <= N, 2 <= D <= 4096, 1 <= batch <= N, 1 <= steps, 0 <= first_step.
+ * w [C][D] (nn.Linear.weight's layout, 8-byte aligned), b [C], mom [C*D + C] (w's buffer, then b's), lr_dev [>= first_step + steps]
+ * on the device, loss_trace [steps], counts [2]: 4-byte aligned.  workspace: rsp_linear_probe_workspace bytes, 8-byte aligned.
+ *   row factor  f_i = scale / sqrtf(ss_i), ss_i = the fp32 sum of squares of row i (each lane of a wave: its float2 columns 2 l,
+ *               2 l + 128, ... by fmaf, x then y; then the wave's xor butterfly -- the search's inverse-norm kernel); f_i = scale with
+ *               normalize = 0.
+ *   valid rows  row i is valid iff ss_i is finite and > 0 (normalize = 0: finite) and 0 <= y_i < C.  An invalid row takes part in
+ *               nothing: the valid rows of every chunk are listed once (in ascending order) and the steps walk that list, so its
+ *               elements are selected away, never multiplied by zero, and with batch = N the fit equals, to the bit, the fit on x
+ *               without those rows.  counts[0] = valid rows of x, counts[1] = invalid ones (integers, from a kernel).
+ *   model       xh_i = x_i * f_i (fp32, when staged); z = xh W^T + b on the fp32 MFMA (a k-ordered fmaf chain), bias added last.
+ *   step t      (t = 0 .. steps - 1) rows [r0, r0 + n), r0 = (t mod ceil(N / batch)) * batch, n = min(batch, N - r0); m = the valid
+ *               rows among them.  loss_trace[t] = (sum over those rows of max_i + logf(sum_c expf(z_ic - max_i)) - z_i[y_i]) / m,
+ *               0 with m = 0.  G_i = (expf(z_i - max_i) / sum_i - onehot(y_i)) / m for a valid row, zeros otherwise.
+ *               dW = G^T xh + wd W, db = sum_i G_i + wd b; buf = (first_step + t == 0) ? d : mu * buf + d; p -= lr[first_step + t] *
+ *               buf -- the rsp_sgd_step rule, weight decay on W and b alike (torch.optim.SGD over fc.parameters()).
+ *   order       a row's max / sum: lane l of a wave takes classes l, l + 64, ... in ascending order, then the xor butterfly; a
+ *               64-row tile's losses in row order, the tiles' partials lane l: l, l + 64, ... then the butterfly.  dW / db: the rows
+ *               of a step are cut into `splits` ranges of 32-row chunks (splits from C, D and the step's m alone), a range runs on the MFMA
+ *               in row order (db: fp32 adds in row order), the ranges are added in fp32 in range order.  No atomics: the same input
+ *               gives the same bits, eagerly or replayed.
+ *   non-finite  a NaN or Inf in w, b, lr or mom propagates as the arithmetic says; one in x, or a label outside [0, C), invalidates
+ *               that row only.
+ * C <= 256: three launches per step (logits, softmax, loss and G in one kernel -- the logits are never stored); four otherwise
+ * (the environment variable RSP_PROBE_GENERAL=1 selects that path at any C: an A/B switch).  The two paths are each held to the rule
+ * and need not agree to the bit.
+ * rsp_linear_probe_logits: logits[i][c] = z_ic of the rule (row pitch ld_out >= C), NaN in every class of an invalid row (validity
+ * without the label condition) -- rsp_xent_metrics then counts the row as a miss.  It needs the first 2 * align256(4 N) bytes of the
+ * workspace: rsp_linear_probe_workspace(N, D, C, b) for any b is enough.
+ * A bad argument is RSP_EINVAL, a workspace below the need RSP_EWORKSPACE, both before anything is launched.  Kernels only, all on
+ * `stream`: no memset, no memcpy, no atomics; capturable after a first eager call.
+ * workspace of fit: f, the flags and the row lists (3 x 4 N), the m of every chunk, G (batch x C), the loss partials (ceil(batch / 64)), the split
+ * partials of dW and db (splits x (C D + C)), each rounded up to 256 bytes.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t rsp_linear_probe_workspace(int32_t N, int32_t D, int32_t C, int32_t batch);
+int rsp_linear_probe_fit(const float* x, int32_t ld, int32_t N, int32_t D, const int64_t* y, int32_t C, int32_t batch,
+                         int32_t first_step, int32_t steps, const float* lr_dev, float mu, float wd, int32_t normalize, float scale,
+                         float* w, float* b, float* mom /* [C*D + C] */, float* loss_trace /* [steps] */, int32_t* counts /* [2] */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int rsp_linear_probe_logits(const float* x, int32_t ld, int32_t N, int32_t D, const float* w, const float* b, int32_t C,
+                            int32_t normalize, float scale, float* logits, int32_t ld_out, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,10 @@ SIGNATURES = {
     "rsp_fingerprint": (C.c_int, [_p, _i32, _i64, _p, _p, _sz, _p]),
     "rsp_repr_stats_workspace": (_sz, [_i32, _i32]),
     "rsp_repr_stats": (C.c_int, [_p, _i32, _i32, _i32, _f, _p, _p, _p, _p, _sz, _p]),
+    "rsp_linear_probe_workspace": (_sz, [_i32, _i32, _i32, _i32]),
+    "rsp_linear_probe_fit": (C.c_int, [_p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _p, _f, _f, _i32, _f, _p, _p, _p, _p, _p, _p,
+                                       _sz, _p]),
+    "rsp_linear_probe_logits": (C.c_int, [_p, _i32, _i32, _i32, _p, _p, _i32, _i32, _f, _p, _i32, _p, _sz, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

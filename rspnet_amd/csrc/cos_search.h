@@ -8,6 +8,19 @@
 
 constexpr int COS_SEARCH_MAXK = 256;      // 4 list slots of 64 ranks
 
+// The fp32 sum of squares of one row of D (even) floats by one wave, the same value in every lane: lane l takes its float2 columns
+// 2 l, 2 l + 128, ... by fmaf, x then y; then the wave's xor butterfly.  inv_norm_kernel (cos_search.hip) and probe_rows_kernel
+// (linear_probe.hip) both call it, so "the sum of squares as the search forms it" is one piece of code.
+__device__ __forceinline__ float rsp_row_sumsq(const float* __restrict__ p, int D, int lane) {
+  float s = 0.f;
+  for (int c = 2 * lane; c < D; c += 128) {
+    const float2 v = *reinterpret_cast<const float2*>(p + c);
+    s = fmaf(v.x, v.x, s);
+    s = fmaf(v.y, v.y, s);
+  }
+  return rsp_wave_sum(s);
+}
+
 // The per-split lists the search left in the workspace: entry (split * Nq + row) * k + rank, sorted by rank; a list that is not
 // full (fewer than k gallery rows in the split) ends in index -1.
 struct CosLists {

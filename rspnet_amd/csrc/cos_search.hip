@@ -32,14 +32,7 @@ static_assert(CS_BQ * CS_SLD <= 2 * CS_BUF, "score tile must fit in the chunk bu
 __global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__ x, int ld, int n, int D, float* __restrict__ inv) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= n) return;
-  const float* p = x + (long long)row * ld;
-  float s = 0.f;
-  for (int c = 2 * lane; c < D; c += 128) {
-    const float2 v = *reinterpret_cast<const float2*>(p + c);
-    s = fmaf(v.x, v.x, s);
-    s = fmaf(v.y, v.y, s);
-  }
-  s = rsp_wave_sum(s);
+  const float s = rsp_row_sumsq(x + (long long)row * ld, D, lane);
   if (lane == 0) inv[row] = s > 0.f ? 1.f / sqrtf(s) : 0.f;
 }
 

@@ -148,6 +148,41 @@ def extract(encoder: nn.Module, loader: Iterable, device, n_crop: int = 1):
     return torch.cat(feats), torch.cat(labels)
 
 
+def synthetic_loaders(bank_samples: int, query_samples: int, batch_size: int, num_classes: int, n_crop: int, T: int, size: int, device,
+                      seed: int = 0):
+    """The monitors' stand-in data: two ``SyntheticLabelledClips``, bank = split 'train' (order fixed by its epoch 0), query = split
+    'val'."""
+    bank = _ft.SyntheticLabelledClips("train", bank_samples, min(batch_size, bank_samples), num_classes, T, size, device, n_crop=n_crop,
+                                      seed=seed)
+    query = _ft.SyntheticLabelledClips("val", query_samples, batch_size, num_classes, T, size, device, n_crop=n_crop, seed=seed)
+    return bank, query
+
+
+def extract_bank_and_query(model: nn.Module, encoder: str, bank_loader: Iterable, query_loader: Iterable, n_crop: int = 1):
+    """(g, y_g, q, y_q, valid): ``extract`` of both loaders through encoder 'q' or 'k' of the pretext model (or its wrapper with
+    ``.module``) in eval mode, every module's ``training`` flag put back afterwards; valid: the query loader's count of real samples.
+    What the kNN monitor and the linear-probe monitor share."""
+    net = getattr(model, "module", model)
+    enc = net.encoder_q if encoder == "q" else net.encoder_k
+    device = next(enc.parameters()).device
+    flags = [(m, m.training) for m in net.modules()]
+    try:
+        net.eval()
+        if encoder == "q" and hasattr(net, "_check_q_weights"):      # a torch-side optimizer leaves the re-pack to the next forward
+            if not net._q_params:
+                net._q_params = list(net.encoder_q.parameters())
+            net._check_q_weights()
+        # a bank of split 'train' has n_crop = 1 clips; only the query side carries crops
+        n_crop_bank = 1 if getattr(bank_loader, "split", None) == "train" else n_crop
+        g, y_g = extract(enc, bank_loader, device, n_crop_bank)
+        q, y_q = extract(enc, query_loader, device, n_crop)
+    finally:
+        for m, was in flags:
+            m.training = was
+    valid = query_loader.num_valid_samples() if hasattr(query_loader, "num_valid_samples") else q.shape[0]
+    return g, y_g, q, y_q, min(int(valid), q.shape[0])
+
+
 class KNNMonitor:
     """Every ``every``-th epoch (and on the last one): weighted kNN accuracy of a labelled query set against a labelled bank on the
     features of one encoder of the pretext model.  ``run`` leaves the model as it found it -- state_dict() bit for bit (eval-mode
@@ -186,37 +221,16 @@ class KNNMonitor:
 
     def build_loaders(self, T: int, size: int, device, seed: int = 0):
         """The stand-in data: two ``SyntheticLabelledClips``, bank = split 'train' (order fixed by its epoch 0), query = split 'val'."""
-        bank = _ft.SyntheticLabelledClips("train", self.bank_samples, min(self.batch_size, self.bank_samples), self.num_classes, T, size,
-                                          device, n_crop=self.n_crop, seed=seed)
-        query = _ft.SyntheticLabelledClips("val", self.query_samples, self.batch_size, self.num_classes, T, size, device,
-                                           n_crop=self.n_crop, seed=seed)
-        return bank, query
+        return synthetic_loaders(self.bank_samples, self.query_samples, self.batch_size, self.num_classes, self.n_crop, T, size, device, seed)
 
     def run(self, model: nn.Module, bank_loader: Iterable, query_loader: Iterable, return_features: bool = False) -> dict:
         """{"acc1", "acc5", "n_bank", "n_query", "seconds"}, with ``return_features`` also "bank_features": the (n_bank, D) backbone
         features it extracted, on the device.  ``model``: the pretext model (or its wrapper with ``.module``)."""
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("KNNMonitor.run: never inside a graph capture")
-        net = getattr(model, "module", model)
-        enc = net.encoder_q if self.encoder == "q" else net.encoder_k
-        device = next(enc.parameters()).device
         t0 = time.perf_counter()
-        flags = [(m, m.training) for m in net.modules()]
-        try:
-            net.eval()
-            if self.encoder == "q" and hasattr(net, "_check_q_weights"):      # a torch-side optimizer leaves the re-pack to the next forward
-                if not net._q_params:
-                    net._q_params = list(net.encoder_q.parameters())
-                net._check_q_weights()
-            # a bank of split 'train' has n_crop = 1 clips; only the query side carries crops
-            n_crop_bank = 1 if getattr(bank_loader, "split", None) == "train" else self.n_crop
-            g, y_g = extract(enc, bank_loader, device, n_crop_bank)
-            q, y_q = extract(enc, query_loader, device, self.n_crop)
-        finally:
-            for m, was in flags:
-                m.training = was
-        valid = query_loader.num_valid_samples() if hasattr(query_loader, "num_valid_samples") else q.shape[0]
-        res = knn_classify(q, y_q, g, y_g, self.k, self.t, self.num_classes, valid=min(int(valid), q.shape[0]))
+        g, y_g, q, y_q, valid = extract_bank_and_query(model, self.encoder, bank_loader, query_loader, self.n_crop)
+        res = knn_classify(q, y_q, g, y_g, self.k, self.t, self.num_classes, valid=valid)
         out = {"acc1": res["acc1"], "acc5": res["acc5"], "n_bank": int(g.shape[0]), "n_query": res["n"],
                "seconds": time.perf_counter() - t0}
         if return_features:

@@ -879,6 +879,57 @@ class HipOps:
                                            _stream()), "rsp_repr_stats")
         return ReprResult(sums, gram, colsum)
 
+    # ---- linear probe on frozen features (linear_probe.hip) ---------------------------------------------------------
+    @staticmethod
+    def _probe_x(who: str, x):
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+            raise _lib.RspError(f"{who}: x must be a float32 HIP device matrix with unit column stride")
+        N, D = x.shape
+        return N, D, x.stride(0) if N > 1 else D
+
+    def linear_probe_fit(self, x, y, w, b, mom, lr, steps: int, batch: Optional[int] = None, first_step: int = 0,
+                         momentum: float = 0.9, weight_decay: float = 1e-4, normalize: bool = True, scale: float = 8.0):
+        """``steps`` SGD steps of the softmax classifier z = (x f) w^T + b on the rows of x (N, D) with labels y (N,) int64, all from
+        one rsp_linear_probe_fit call (include/rspnet_hip.h states the rule).  w (C, D), b (C,) and mom (C * D + C,) are updated in
+        place; lr: the device vector of learning rates, indexed by first_step + t.  Returns (loss_trace fp32 (steps,), counts int32
+        (2,): valid and invalid rows).  Rows of x may be strided (unit column stride, even row pitch)."""
+        N, D, ld = self._probe_x("linear_probe_fit", x)
+        _chk(y, "y", torch.int64)
+        for n, t in (("w", w), ("b", b), ("mom", mom), ("lr", lr)):
+            _chk(t, n)
+        Cc = w.shape[0]
+        if w.dim() != 2 or w.shape[1] != D or b.numel() != Cc or mom.numel() != Cc * D + Cc or y.numel() != N:
+            raise _lib.RspError(f"linear_probe_fit: x {tuple(x.shape)}, y {tuple(y.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}, "
+                                f"mom {tuple(mom.shape)} do not fit")
+        steps, first_step = int(steps), int(first_step)
+        batch = N if batch is None else int(batch)
+        if steps >= 1 and first_step >= 0 and lr.numel() < first_step + steps:
+            raise _lib.RspError(f"linear_probe_fit: {lr.numel()} learning rates for steps up to {first_step + steps}")
+        dev = x.device
+        loss = torch.empty(max(steps, 1), dtype=torch.float32, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        wsb = int(self.lib.rsp_linear_probe_workspace(N, D, Cc, batch))      # (0 for sizes the call itself rejects, before any launch)
+        ws = self._workspace(dev, wsb)
+        _lib.check(self.lib.rsp_linear_probe_fit(_ptr(x), ld, N, D, _ptr(y), Cc, batch, first_step, steps, _ptr(lr), float(momentum),
+                                                 float(weight_decay), int(bool(normalize)), float(scale), _ptr(w), _ptr(b), _ptr(mom),
+                                                 _ptr(loss), _ptr(counts), _ptr(ws), wsb, _stream()), "rsp_linear_probe_fit")
+        return loss[:steps], counts
+
+    def linear_probe_logits(self, x, w, b, normalize: bool = True, scale: float = 8.0):
+        """logits (N, C) of the probe (w, b) on the rows of x (rsp_linear_probe_logits): NaN in every class of an invalid row."""
+        N, D, ld = self._probe_x("linear_probe_logits", x)
+        _chk(w, "w")
+        _chk(b, "b")
+        Cc = w.shape[0]
+        if w.dim() != 2 or w.shape[1] != D or b.numel() != Cc:
+            raise _lib.RspError(f"linear_probe_logits: x {tuple(x.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)} do not fit")
+        logits = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+        wsb = int(self.lib.rsp_linear_probe_workspace(N, D, Cc, 1))
+        ws = self._workspace(x.device, wsb)
+        _lib.check(self.lib.rsp_linear_probe_logits(_ptr(x), ld, N, D, _ptr(w), _ptr(b), Cc, int(bool(normalize)), float(scale),
+                                                    _ptr(logits), Cc, _ptr(ws), wsb, _stream()), "rsp_linear_probe_logits")
+        return logits
+
     # ---- fine-tune criterion, accuracy and meters (classify.hip) -------------------------------------------------
     def xent_metrics(self, logits, target, n_crop: int = 1, valid: Optional[int] = None, want_grad: bool = True, meters=None):
         """Crop mean, cross-entropy (loss and, with want_grad, its gradient with respect to the crop logits), top-1 / top-5

@@ -22,7 +22,7 @@ from pathlib import Path
 
 import torch
 
-from . import _lib, fingerprint, knn, ops, repr_stats
+from . import _lib, fingerprint, knn, linear_probe, ops, repr_stats
 from .framework.arguments import RUN_DIR_NAME_REGEX, add_driver_arguments, parse_driver_args, save_run_files  # noqa: F401
 from .framework.driver import (append_scalars, finish_process_group, init_process_group, launch, load_config, load_states, save_run,
                                seed_everything, setup_logging, visible_gpu_count)
@@ -185,6 +185,13 @@ class Engine:
         # queue (rank-identical by construction); no labels, no loaders
         self.repr_monitor = repr_stats.ReprMonitor.from_config(cfg, self.num_epochs)
         self._repr_result, self._bank_features = None, None
+        # opt-in (config key "probe_monitor", e.g. -x '{"probe_monitor": {"every": 10, "num_classes": 101, "steps": 100}}'): None
+        # otherwise.  Rank 0 fits a linear probe on the bank's features and evaluates it on the query's; the loaders are its own
+        # (the kNN monitor's keys and stand-in data), so the two monitors extract separately
+        self.probe = linear_probe.LinearProbeMonitor.from_config(cfg, self.num_epochs)
+        self.probe_loaders, self._probe_result = None, None
+        if self.probe is not None and local_rank == 0:
+            self.probe_loaders = self.probe.build_loaders(T, size, self.device, seed=args.seed)
 
     # ---- checkpoints (pretrain.py:112-132) ---------------------------------------------------------------------------
     def load_checkpoint(self, path):
@@ -273,6 +280,8 @@ class Engine:
             rec.update({"knn/acc1": self._knn_result["acc1"], "knn/acc5": self._knn_result["acc5"]})
         if self._repr_result is not None:
             rec.update(self._repr_result)
+        if self._probe_result is not None:
+            rec.update({f"probe_{k}": self._probe_result[k] for k in ("acc1", "acc5", "loss")})
         append_scalars(self.scalars_path, rec)
 
     def _run_knn_monitor(self):
@@ -316,6 +325,22 @@ class Engine:
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             torch.distributed.barrier()
 
+    def _run_probe_monitor(self):
+        """After the other monitors and before the epoch's scalar line: rank 0 extracts, fits and evaluates eagerly on the current
+        stream (train_epoch has waited for the epoch's last step; nothing here is captured); the other ranks wait at a barrier.
+        Has run on one GPU only."""
+        self._probe_result = None
+        m = self.probe
+        if m is None or not m.due(self.current_epoch):
+            return
+        if self.local_rank == 0:
+            r = self._probe_result = m.run(self.model, *self.probe_loaders)
+            logger.info(f"Probe [{self.current_epoch}/{self.num_epochs}]\tAcc@1 {r['acc1']:.2f}\tAcc@5 {r['acc5']:.2f}\tloss {r['loss']:.4f}"
+                        f"\t({m.steps} steps, lr {m.lr}, bank {r['n_bank']}, query {r['n_query']}, {r['bad_rows']} bad, "
+                        f"{r['seconds']:.1f} s)")
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            torch.distributed.barrier()
+
     def run(self):
         num_epochs = 1 if self.args.debug else self.num_epochs
         self._first_epoch = self.current_epoch
@@ -332,6 +357,7 @@ class Engine:
             stats = self.train_epoch()
             self._run_knn_monitor()
             self._run_repr_monitor()
+            self._run_probe_monitor()
             self.scheduler.step()
             self._write_scalars(lr)
             self.current_epoch += 1
