@@ -87,7 +87,9 @@ int rsp_conv3d_dgrad(const rsp_conv3d_desc* d, const float* dy, const float* w_r
                      size_t workspace_bytes, void* stream);
 
 /* dgrad over weights already re-packed into the per-stride-class layouts (rsp_conv3d_pack_jobs(which = 1) + rsp_pack_run):
- * the workspace then only holds the K-split partials (rsp_conv3d_dgrad_workspace(d) is always enough). */
+ * the workspace then only holds the K-split partials (rsp_conv3d_dgrad_workspace(d) is always enough).
+ * rsp_conv3d_packed_dgrad_elems is an upper bound: the jobs write the sum of their O x Kld floats from w_packed on and the rest of
+ * the buffer is neither written nor read (it may stay uninitialised; tests/test_pack_gpu.py keeps NaNs there). */
 size_t rsp_conv3d_packed_dgrad_elems(const rsp_conv3d_desc* d);
 int rsp_conv3d_dgrad_packed(const rsp_conv3d_desc* d, const float* dy, const float* w_packed, float* dx, void* workspace,
                             size_t workspace_bytes, void* stream);

@@ -3050,7 +3050,7 @@ int32_t rsp_conv3d_pack_jobs(const rsp_conv3d_desc* d, int32_t which, int32_t Co
     j.blocks = pk.O;
   };
   if (which == 0) {
-    if (max_jobs < 1) return RSP_EINVAL;
+    RSP_REQUIRE(max_jobs >= 1, "rsp_conv3d_pack_jobs: max_jobs too small (the forward layout is one job)");
     if (rsp_stem_applicable(d)) {
       rsp_pack_job& j = jobs[0];
       memset(&j, 0, sizeof j);
@@ -3078,7 +3078,7 @@ int32_t rsp_conv3d_pack_jobs(const rsp_conv3d_desc* d, int32_t which, int32_t Co
   for (int c = 0; c < nclass; ++c) {
     const DgradClass g = dgrad_class(d, c);
     if (g.nt * g.nh * g.nw == 0 || g.Gd * g.Gh * g.Gw == 0) continue;
-    if (n >= max_jobs) return RSP_EINVAL;
+    RSP_REQUIRE(n < max_jobs, "rsp_conv3d_pack_jobs: max_jobs too small (one job per non-empty stride-parity class)");
     PackParams pk;
     dgrad_pack_params(d, g, w_ref, w_packed + woff, pk);
     fill(jobs[n++], pk);

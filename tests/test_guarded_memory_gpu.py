@@ -1,6 +1,6 @@
 """GPU: the per-kernel test bodies again, with every operand inside guarded memory (tests/guarded.py).
 
-Each body of test_kernels_gpu / test_bn_eval_bwd_gpu / test_retrieval_gpu / test_knn_gpu listed below runs unchanged, at its own cases
+Each body of test_kernels_gpu / test_bn_eval_bwd_gpu / test_retrieval_gpu / test_knn_gpu / test_pack_gpu listed below runs unchanged, at its own cases
 and tolerances, while the module's dev() / dev_empty() hand out guarded allocations and rspnet_amd.ops allocates its outputs and
 workspaces from the guard too.  The body's comparison against CpuOps / fp64 stays the value check (a read outside an operand meets the
 NaN moat and fails it); Guarded.check() then asserts that no band byte changed, no input changed and no float32 output of the op kept
@@ -21,6 +21,7 @@ import torch
 import test_bn_eval_bwd_gpu as B
 import test_kernels_gpu as K
 import test_knn_gpu as Q
+import test_pack_gpu as P
 import test_retrieval_gpu as R
 from guarded import Guarded
 from rspnet_amd.ops import ConvGeom
@@ -67,6 +68,9 @@ BODIES += [(B, "test_bn_eval_act_pool_bwd_matches_autograd", 16)]
 BODIES += [(R, "test_cosine_topk_edges", 8), (R, "test_zero_rows_and_strided_inputs", 8)]
 BODIES += [(Q, "test_knn_matches_fp64_reference", 8), (Q, "test_zero_rows_bad_labels_and_valid", 8),
            (Q, "test_tie_straddling_rank_k_goes_to_the_lower_index", 8)]
+# the batched re-pack and the input gradient over its buffers: the dgrad buffers' unowned tails stay the NaN pattern (the bodies
+# declare them and look at the word set themselves), the workspace is the NaN pattern too, and dx must come out finite and whole
+BODIES += [(P, name, 16) for name in ("test_forward_layout_equals_the_single_packer", "test_packed_dgrad", "test_one_table_many_jobs")]
 
 GUARDED = [pytest.param(mod, name, skew, kw, id=f"{name}[{label}]" if label else name)
            for mod, name, skew in BODIES for label, kw in _cases_of(getattr(mod, name))]
@@ -75,8 +79,10 @@ GUARDED = [pytest.param(mod, name, skew, kw, id=f"{name}[{label}]" if label else
 @contextlib.contextmanager
 def placed_in(mod, G):
     """The module's device placement pointed at the guard, for the length of one body."""
-    saved = {n: getattr(mod, n) for n in ("dev", "dev_empty") if hasattr(mod, n)}
+    saved = {n: getattr(mod, n) for n in ("dev", "dev_empty", "GUARD") if hasattr(mod, n)}
     try:
+        if "GUARD" in saved:      # (a module whose ops leave part of an output unwritten by contract tells the guard which)
+            mod.GUARD = G
         if mod is Q:      # (its dev() takes numpy arrays and returns a list)
             mod.dev = lambda *arrays: [G.put(torch.from_numpy(np.array(a))) for a in arrays]
         else:
