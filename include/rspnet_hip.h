@@ -739,6 +739,66 @@ int rsp_linear_probe_logits(const float* x, int32_t ld, int32_t N, int32_t D, co
                             int32_t normalize, float scale, float* logits, int32_t ld_out, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Clustering evaluation (cluster.hip; the project's own, no counterpart in the reference): spherical k-means on N stored feature
+ * rows, all max_iters iterations issued from ONE call, stopped on the device, nothing read back; and the cluster x label table behind
+ * NMI, ARI and purity.  Additive: the ABI version stays 130.
+ * x: N x D fp32 row-major with row pitch ld; D and ld even, ld >= D, the base 8-byte aligned (the rule of the cosine search).
+ * cent [C][D] (pitch D, 8-byte aligned): in = the initial centroids, out = the final ones.  1 <= N <= 262144, 2 <= D <= 4096,
+ * 1 <= C <= 1024, 1 <= L <= 1024, 1 <= max_iters <= 1000.  assign [N], counts [C], changed_trace [max_iters]: int32, 4-byte aligned;
+ * objective_trace [max_iters] (fp64), info and the workspace (rsp_kmeans_workspace bytes): 8-byte aligned.
+ *   validity    ss_i = the fp32 sum of squares of row i as the search forms it (rsp_row_sumsq: each lane of a wave its float2 columns
+ *               2 l, 2 l + 128, ... by fmaf, x then y; then the wave's xor butterfly).  Row i is valid iff ss_i is finite and > 0.  An
+ *               invalid row gets assign = -1, is counted in rows_bad and takes part in nothing: the valid rows are listed once, in
+ *               ascending order, and every kernel walks that list by rank, so its elements are selected away, never multiplied by
+ *               zero, and the fit equals, to the bit, the fit on x without those rows.
+ *   assignment  assign[i] = the single neighbour rsp_cosine_topk(q = x, g = cent, k = 1) returns for row i, sim[i] its similarity
+ *               s = (x_i . m_c) * inv_i * inv_c in fp32 -- the search itself runs, there is no second expression.  A zero centroid
+ *               has inverse norm 0 (s = 0); a centroid holding a NaN or an Inf is never returned; an exact tie goes to the LOWER
+ *               cluster index.  A valid row for which no centroid is returnable gets -1 (sim NaN) and is counted in `unassigned`.
+ *   iteration   t = 0 .. max_iters - 1: assign from the current cent.  changed_trace[t] = the rows whose assignment differs from
+ *               iteration t - 1 (t = 0: rows_valid).  objective_trace[t] = the sum of sim over the assigned rows / their number, 0
+ *               with none: the fp32 values added in fp64 -- a block of 256 list ranks by the wave's xor butterfly and then its four
+ *               waves in order, the blocks lane l: l, l + 64, ... in order and then the butterfly.  If t > 0 and changed_trace[t] ==
+ *               0: converged = 1, iters_run = t + 1 and nothing is updated further.  Otherwise the update: for a cluster with
+ *               counts[c] > 0, cent[c][a] = the sum over the rows with assign == c of xh_ia, xh = x * inv_i formed in fp32 when
+ *               staged, left unnormalised (the search normalises); a cluster with counts[c] == 0 keeps its centroid.  The update
+ *               also follows the last iteration of a fit that has not converged: the returned cent is always the sum over the
+ *               returned assign, and counts its bincount.
+ *   order       the update is onehot(assign)^T xh on the fp32 MFMA: the listed rows are cut into `splits` ranges of 32-row chunks
+ *               (splits from C, D and rows_valid alone); inside a range an element of cent is the fp32 sum of its rows' xh in
+ *               ascending row order (1 * v and 0 * v are exact, a k-ordered fmaf chain); the ranges are added in fp32 in range
+ *               order.  No float atomics: the same input gives the same bits, eagerly or replayed.
+ *   traces      entries t >= iters_run: changed_trace = -1, objective_trace = NaN.  Every element of cent (of a non-empty cluster),
+ *               assign, counts, both traces and info is written on every call.
+ *   info        rows_valid, rows_bad; iters_run (max_iters when not converged), converged; empty = the clusters with count 0 and
+ *               unassigned = the valid rows with assign -1, both in the returned assignment.
+ *   stop        the call issues the launches of all max_iters iterations (six each after the first); behind the stop they read a device
+ *               flag and return at once.  No read-back, no synchronisation inside the call.
+ * rsp_kmeans_assign: assign / sim (sim may be NULL) of the rule for the rows of x against given centroids, no update.  workspace:
+ * rsp_cosine_topk_workspace(N, C, D, 1, 0) bytes (rsp_kmeans_workspace(N, D, C) is enough).
+ * rsp_contingency: table[c][l] = the number of i with assign[i] == c and y[i] == l (y int64, 8-byte aligned, as table and dropped);
+ * rows with assign outside [0, C) -- the -1 rows -- or y outside [0, L) are counted in dropped[0].  Exact integers (the table is
+ * zeroed by a kernel, then integer atomic adds); every element of the table is written.
+ * A bad argument is RSP_EINVAL with the entry point's name in rsp_last_error(), a workspace below the query RSP_EWORKSPACE, both
+ * before anything is launched.  Kernels only, all on `stream`: no memset, no memcpy, no float atomics; capturable after a first eager call.
+ * workspace of fit: the search's (inverse norms and k = 1 lists), the state, the row list (4 N), the block partials (16 per 256 rows),
+ * the split partials of cent and counts (splits x (C D + C)), each rounded up to 256 bytes.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct rsp_kmeans_info {      /* device struct, 32 bytes */
+  int64_t rows_valid, rows_bad;
+  int32_t iters_run, converged, empty, unassigned;
+} rsp_kmeans_info;
+size_t rsp_kmeans_workspace(int32_t N, int32_t D, int32_t C);
+int rsp_kmeans_fit(const float* x, int32_t ld, int32_t N, int32_t D, float* cent /* [C][D]: in = initial, out = final */, int32_t C,
+                   int32_t max_iters, int32_t* assign /* [N] */, int32_t* counts /* [C] */, int32_t* changed_trace /* [max_iters] */,
+                   double* objective_trace /* [max_iters] */, rsp_kmeans_info* info, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int rsp_kmeans_assign(const float* x, int32_t ld, int32_t N, int32_t D, const float* cent, int32_t C, int32_t* assign /* [N] */,
+                      float* sim /* [N], nullable */, void* workspace, size_t workspace_bytes, void* stream);
+int rsp_contingency(const int32_t* assign, const int64_t* y, int32_t N, int32_t C, int32_t L, int64_t* table /* [C][L] */,
+                    int64_t* dropped /* [1] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,12 @@ class ReprSums(C.Structure):
                 ("rows_bad", C.c_int64)]
 
 
+class KmeansInfo(C.Structure):
+    """rsp_kmeans_info (32 bytes)"""
+    _fields_ = [("rows_valid", C.c_int64), ("rows_bad", C.c_int64), ("iters_run", C.c_int32), ("converged", C.c_int32),
+                ("empty", C.c_int32), ("unassigned", C.c_int32)]
+
+
 _PD = C.POINTER(ConvDesc)
 _PP = C.POINTER(PoolDesc)
 _sz = C.c_size_t
@@ -186,6 +192,10 @@ SIGNATURES = {
     "rsp_linear_probe_fit": (C.c_int, [_p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _p, _f, _f, _i32, _f, _p, _p, _p, _p, _p, _p,
                                        _sz, _p]),
     "rsp_linear_probe_logits": (C.c_int, [_p, _i32, _i32, _i32, _p, _p, _i32, _i32, _f, _p, _i32, _p, _sz, _p]),
+    "rsp_kmeans_workspace": (_sz, [_i32, _i32, _i32]),
+    "rsp_kmeans_fit": (C.c_int, [_p, _i32, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "rsp_kmeans_assign": (C.c_int, [_p, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _sz, _p]),
+    "rsp_contingency": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

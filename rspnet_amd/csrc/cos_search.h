@@ -27,6 +27,8 @@ struct CosLists {
   float* val;
   int* idx;
   int splits;
+  const float* inv_q;      // the inverse norms the search left at the head of the workspace: [Nq], then inv_g [Ng]
+  const float* inv_g;
 };
 
 // The size, k and alignment checks both entry points make on q and g; `who` is the entry point's name in the message.
@@ -34,6 +36,11 @@ int rsp_cos_search_check(const char* who, const float* q, int ldq, int Nq, const
 // Checks and carves the workspace (rsp_cosine_topk_workspace bytes), runs the inverse norms of q and g and then the search.
 int rsp_cos_search(const char* who, const float* q, int ldq, int Nq, const float* g, int ldg, int Ng, int D, int k, int splits,
                    void* workspace, size_t workspace_bytes, hipStream_t s, CosLists* lists);
+// The same search for a caller that issues it many times over one query matrix (rsp_kmeans_fit): stop, when not nullptr, is a device
+// flag that turns every launch into a no-op while it is not 0; norm_q = false keeps the query norms of an earlier call on the same
+// workspace.  rsp_cos_search is this with (nullptr, true).
+int rsp_cos_search_gated(const char* who, const float* q, int ldq, int Nq, const float* g, int ldg, int Ng, int D, int k, int splits,
+                         void* workspace, size_t workspace_bytes, hipStream_t s, CosLists* lists, const int* stop, bool norm_q);
 
 // A wave's sorted list of k entries in S = ceil(k / 64) register slots per lane: rank r lives in slot r / 64, lane r % 64.
 // kmask: the lanes of the LAST slot that belong to the list (the slots below it are full).

@@ -9,12 +9,14 @@
 //
 // Kernels:
 //   inv_norm_kernel      one wave per row: 1/|x| (0 for a zero row) of the query and gallery rows, into the workspace.
-//   cos_topk_kernel<S>   block = 64 queries x one gallery split.  Per gallery tile of 128 rows the 4 waves (2 x 2, 32 x 64 each)
+//   cos_topk_kernel<S, K1>   block = 64 queries x one gallery split.  Per gallery tile of 128 rows the 4 waves (2 x 2, 32 x 64 each)
 //                        accumulate the dot products on v_mfma_f32_32x32x2_f32 from LDS chunks of 32 k (register prefetch of the
 //                        next chunk, double-buffered LDS), scale them to similarities into an LDS score tile (aliasing the chunk
 //                        buffers), and each wave updates the running top-k of 16 queries: its lists live in registers (16 x S x 2
 //                        VGPRs, S = ceil(k / 64), cos_search.h); tile scores above the current k-th best are inserted in ascending
 //                        gallery order (ballot + shift), which keeps the tie rule.  The split's list goes to the workspace.
+//                        K1 (k = 1: the assignment step of rsp_kmeans_fit, and any search for one neighbour): the insertion is
+//                        replaced by the wave's arg-max of the tile (lower index on a tie), the same entry at a fraction of the cost.
 #include "cos_search.h"
 
 namespace {
@@ -29,19 +31,23 @@ constexpr size_t CS_LDS_BYTES = (size_t)2 * CS_BUF * sizeof(float);
 
 static_assert(CS_BQ * CS_SLD <= 2 * CS_BUF, "score tile must fit in the chunk buffers it aliases");
 
-__global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__ x, int ld, int n, int D, float* __restrict__ inv) {
+// stop (here and in cos_topk_kernel): nullptr, or a device flag that makes the whole launch return at once when it is not 0 (the
+// iterations rsp_kmeans_fit issues past its device-side stop).
+__global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__ x, int ld, int n, int D, float* __restrict__ inv,
+                                                       const int* __restrict__ stop) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= n) return;
+  if (row >= n || (stop && *stop)) return;
   const float s = rsp_row_sumsq(x + (long long)row * ld, D, lane);
   if (lane == 0) inv[row] = s > 0.f ? 1.f / sqrtf(s) : 0.f;
 }
 
-template <int S>
+template <int S, bool K1>
 __global__ __launch_bounds__(256) void cos_topk_kernel(const float* __restrict__ q, int ldq, int Nq, const float* __restrict__ g,
                                                        int ldg, int Ng, int D, int k, int splits, const float* __restrict__ invq,
                                                        const float* __restrict__ invg, float* __restrict__ part_val,
-                                                       int* __restrict__ part_idx) {
+                                                       int* __restrict__ part_idx, const int* __restrict__ stop) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  if (stop && *stop) return;      // (the whole block, before any barrier)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int l32 = lane & 31, h = lane >> 5;
   const int wq = wave >> 1, wg = wave & 1;
@@ -142,20 +148,49 @@ __global__ __launch_bounds__(256) void cos_topk_kernel(const float* __restrict__
       }
     }
     __syncthreads();
+    if constexpr (K1) {
+      // k = 1: the tile's maximum of each query by the whole wave -- the lower index on a tie, a NaN or -inf score is no candidate --
+      // taken only when strictly greater than the running one: the entry the insertion below leaves in a one-entry list
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float* srow = sm + (16 * wave + r) * CS_SLD;
-      const float thr = __shfl(tv[r][S - 1], k - 1 - 64 * (S - 1));      // the current k-th best (a NaN score never passes)
-      unsigned long long m0 = __ballot(srow[lane] > thr), m1 = __ballot(srow[lane + 64] > thr);
-      while (m0) {
-        const int j = __ffsll((long long)m0) - 1;
-        m0 &= m0 - 1;
-        list_insert<S>(tv[r], ti[r], srow[j], g0 + j, k, kmask, lane);
+      for (int r = 0; r < 16; ++r) {
+        const float* srow = sm + (16 * wave + r) * CS_SLD;
+        const float v0 = srow[lane], v1 = srow[lane + 64];
+        float bv = v0 == v0 ? v0 : -INFINITY;
+        int bj = lane;
+        if (v1 > bv) {
+          bv = v1;
+          bj = lane + 64;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const float ov = __shfl_xor(bv, o);
+          const int oj = __shfl_xor(bj, o);
+          if (ov > bv || (ov == bv && oj < bj)) {
+            bv = ov;
+            bj = oj;
+          }
+        }
+        if (bv > tv[r][0]) {
+          tv[r][0] = bv;
+          ti[r][0] = g0 + bj;
+        }
       }
-      while (m1) {
-        const int j = __ffsll((long long)m1) - 1;
-        m1 &= m1 - 1;
-        list_insert<S>(tv[r], ti[r], srow[64 + j], g0 + 64 + j, k, kmask, lane);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float* srow = sm + (16 * wave + r) * CS_SLD;
+        const float thr = __shfl(tv[r][S - 1], k - 1 - 64 * (S - 1));      // the current k-th best (a NaN score never passes)
+        unsigned long long m0 = __ballot(srow[lane] > thr), m1 = __ballot(srow[lane + 64] > thr);
+        while (m0) {
+          const int j = __ffsll((long long)m0) - 1;
+          m0 &= m0 - 1;
+          list_insert<S>(tv[r], ti[r], srow[j], g0 + j, k, kmask, lane);
+        }
+        while (m1) {
+          const int j = __ffsll((long long)m1) - 1;
+          m1 &= m1 - 1;
+          list_insert<S>(tv[r], ti[r], srow[64 + j], g0 + 64 + j, k, kmask, lane);
+        }
       }
     }
     __syncthreads();      // the next tile's first chunk overwrites the score tile
@@ -176,17 +211,17 @@ __global__ __launch_bounds__(256) void cos_topk_kernel(const float* __restrict__
   }
 }
 
-template <int S>
+template <int S, bool K1 = false>
 int launch_search(const float* q, int ldq, int Nq, const float* g, int ldg, int Ng, int D, int k, int splits, const float* invq,
-                  const float* invg, float* part_val, int* part_idx, hipStream_t s) {
+                  const float* invg, float* part_val, int* part_idx, const int* stop, hipStream_t s) {
   static bool attr_set = false;      // the instance's own: its dynamic LDS exceeds the default limit
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cos_topk_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cos_topk_kernel<S, K1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)CS_LDS_BYTES);
     attr_set = true;
   }
-  hipLaunchKernelGGL(cos_topk_kernel<S>, dim3(rsp_cdiv(Nq, CS_BQ), splits), dim3(256), CS_LDS_BYTES, s, q, ldq, Nq, g, ldg, Ng, D, k,
-                     splits, invq, invg, part_val, part_idx);
+  hipLaunchKernelGGL((cos_topk_kernel<S, K1>), dim3(rsp_cdiv(Nq, CS_BQ), splits), dim3(256), CS_LDS_BYTES, s, q, ldq, Nq, g, ldg, Ng, D, k,
+                     splits, invq, invg, part_val, part_idx, stop);
   return rsp_check_launch("cos_topk_kernel");
 }
 
@@ -230,6 +265,11 @@ int rsp_cos_search_check(const char* who, const float* q, int ldq, int Nq, const
 
 int rsp_cos_search(const char* who, const float* q, int ldq, int Nq, const float* g, int ldg, int Ng, int D, int k, int splits,
                    void* workspace, size_t workspace_bytes, hipStream_t s, CosLists* lists) {
+  return rsp_cos_search_gated(who, q, ldq, Nq, g, ldg, Ng, D, k, splits, workspace, workspace_bytes, s, lists, nullptr, true);
+}
+
+int rsp_cos_search_gated(const char* who, const float* q, int ldq, int Nq, const float* g, int ldg, int Ng, int D, int k, int splits,
+                         void* workspace, size_t workspace_bytes, hipStream_t s, CosLists* lists, const int* stop, bool norm_q) {
   if (workspace_bytes < rsp_cosine_topk_workspace(Nq, Ng, D, k, splits)) return fail(who, "workspace too small", RSP_EWORKSPACE);
   splits = rsp_cosine_topk_splits(Nq, Ng, splits);
   float* invq = reinterpret_cast<float*>(workspace);
@@ -238,16 +278,22 @@ int rsp_cos_search(const char* who, const float* q, int ldq, int Nq, const float
   lists->val = reinterpret_cast<float*>(part);
   lists->idx = reinterpret_cast<int*>(part + (size_t)splits * Nq * k * sizeof(float));
   lists->splits = splits;
-  hipLaunchKernelGGL(inv_norm_kernel, dim3(rsp_cdiv(Nq, 4)), dim3(256), 0, s, q, ldq, Nq, D, invq);
-  int rc = rsp_check_launch("inv_norm_kernel");
-  if (rc != RSP_OK) return rc;
-  hipLaunchKernelGGL(inv_norm_kernel, dim3(rsp_cdiv(Ng, 4)), dim3(256), 0, s, g, ldg, Ng, D, invg);
+  lists->inv_q = invq;
+  lists->inv_g = invg;
+  int rc = RSP_OK;
+  if (norm_q) {
+    hipLaunchKernelGGL(inv_norm_kernel, dim3(rsp_cdiv(Nq, 4)), dim3(256), 0, s, q, ldq, Nq, D, invq, stop);
+    rc = rsp_check_launch("inv_norm_kernel");
+    if (rc != RSP_OK) return rc;
+  }
+  hipLaunchKernelGGL(inv_norm_kernel, dim3(rsp_cdiv(Ng, 4)), dim3(256), 0, s, g, ldg, Ng, D, invg, stop);
   rc = rsp_check_launch("inv_norm_kernel");
   if (rc != RSP_OK) return rc;
+  if (k == 1) return launch_search<1, true>(q, ldq, Nq, g, ldg, Ng, D, k, splits, invq, invg, lists->val, lists->idx, stop, s);
   switch (rsp_cdiv(k, 64)) {
-    case 1: return launch_search<1>(q, ldq, Nq, g, ldg, Ng, D, k, splits, invq, invg, lists->val, lists->idx, s);
-    case 2: return launch_search<2>(q, ldq, Nq, g, ldg, Ng, D, k, splits, invq, invg, lists->val, lists->idx, s);
-    case 3: return launch_search<3>(q, ldq, Nq, g, ldg, Ng, D, k, splits, invq, invg, lists->val, lists->idx, s);
-    default: return launch_search<4>(q, ldq, Nq, g, ldg, Ng, D, k, splits, invq, invg, lists->val, lists->idx, s);
+    case 1: return launch_search<1>(q, ldq, Nq, g, ldg, Ng, D, k, splits, invq, invg, lists->val, lists->idx, stop, s);
+    case 2: return launch_search<2>(q, ldq, Nq, g, ldg, Ng, D, k, splits, invq, invg, lists->val, lists->idx, stop, s);
+    case 3: return launch_search<3>(q, ldq, Nq, g, ldg, Ng, D, k, splits, invq, invg, lists->val, lists->idx, stop, s);
+    default: return launch_search<4>(q, ldq, Nq, g, ldg, Ng, D, k, splits, invq, invg, lists->val, lists->idx, stop, s);
   }
 }

@@ -201,6 +201,7 @@ def _dy_target(y, in_ld: int, dy_out):
 
 KnnResult = collections.namedtuple("KnnResult", "pred rank hits votes idx dist")      # of HipOps.knn_classify
 ReprResult = collections.namedtuple("ReprResult", "sums gram colsum")                  # of HipOps.repr_stats
+KmeansResult = collections.namedtuple("KmeansResult", "assign counts changed objective info")      # of HipOps.kmeans_fit
 
 
 class HipOps:
@@ -929,6 +930,59 @@ class HipOps:
         _lib.check(self.lib.rsp_linear_probe_logits(_ptr(x), ld, N, D, _ptr(w), _ptr(b), Cc, int(bool(normalize)), float(scale),
                                                     _ptr(logits), Cc, _ptr(ws), wsb, _stream()), "rsp_linear_probe_logits")
         return logits
+
+    # ---- clustering evaluation (cluster.hip) -------------------------------------------------------------------------
+    def kmeans_fit(self, x, cent, max_iters: int):
+        """Spherical k-means on the rows of x (N, D) from the centroids cent (C, D), updated in place, all ``max_iters`` iterations from
+        one rsp_kmeans_fit call (include/rspnet_hip.h states the rule).  Returns the named tuple (assign int32 (N,), counts int32
+        (C,), changed int32 (max_iters,), objective fp64 (max_iters,), info: the 32-byte rsp_kmeans_info as a uint8 device tensor).
+        Rows of x may be strided (unit column stride, even row pitch)."""
+        N, D, ld = self._probe_x("kmeans_fit", x)
+        _chk(cent, "cent")
+        if cent.dim() != 2 or cent.shape[1] != D:
+            raise _lib.RspError(f"kmeans_fit: x {tuple(x.shape)} and cent {tuple(cent.shape)} do not fit")
+        Cc, iters, dev = cent.shape[0], int(max_iters), x.device
+        assign = torch.empty(N, dtype=torch.int32, device=dev)
+        counts = torch.empty(Cc, dtype=torch.int32, device=dev)
+        changed = torch.empty(max(iters, 1), dtype=torch.int32, device=dev)
+        objective = torch.empty(max(iters, 1), dtype=torch.float64, device=dev)
+        info = torch.empty(C.sizeof(_lib.KmeansInfo), dtype=torch.uint8, device=dev)
+        wsb = int(self.lib.rsp_kmeans_workspace(N, D, Cc))      # (0 for sizes the call itself rejects, before any launch)
+        ws = self._workspace(dev, wsb)
+        _lib.check(self.lib.rsp_kmeans_fit(_ptr(x), ld, N, D, _ptr(cent), Cc, iters, _ptr(assign), _ptr(counts), _ptr(changed),
+                                           _ptr(objective), _ptr(info), _ptr(ws), wsb, _stream()), "rsp_kmeans_fit")
+        return KmeansResult(assign, counts, changed[:iters], objective[:iters], info)
+
+    def kmeans_assign(self, x, cent, want_sim: bool = True):
+        """(assign int32 (N,), sim fp32 (N,) | None) of the rows of x against the centroids cent (rsp_kmeans_assign): the cosine
+        search's single neighbour, -1 / NaN for an invalid row."""
+        N, D, ld = self._probe_x("kmeans_assign", x)
+        _chk(cent, "cent")
+        if cent.dim() != 2 or cent.shape[1] != D:
+            raise _lib.RspError(f"kmeans_assign: x {tuple(x.shape)} and cent {tuple(cent.shape)} do not fit")
+        Cc, dev = cent.shape[0], x.device
+        assign = torch.empty(N, dtype=torch.int32, device=dev)
+        sim = torch.empty(N, dtype=torch.float32, device=dev) if want_sim else None
+        wsb = int(self.lib.rsp_cosine_topk_workspace(N, Cc, D, 1, 0))
+        ws = self._workspace(dev, wsb)
+        _lib.check(self.lib.rsp_kmeans_assign(_ptr(x), ld, N, D, _ptr(cent), Cc, _ptr(assign), _ptr(sim), _ptr(ws), wsb, _stream()),
+                   "rsp_kmeans_assign")
+        return assign, sim
+
+    def contingency(self, assign, y, num_clusters: int, num_classes: int):
+        """(table int64 (num_clusters, num_classes), dropped int64 (1,)): table[c][l] = #{i: assign[i] == c, y[i] == l}; the rows
+        with assign < 0 or a label outside [0, num_classes) are counted in dropped (rsp_contingency)."""
+        _chk(assign, "assign", torch.int32)
+        _chk(y, "y", torch.int64)
+        if assign.dim() != 1 or y.numel() != assign.numel():
+            raise _lib.RspError(f"contingency: {assign.numel()} assignments, {y.numel()} labels")
+        Cc, L, dev = int(num_clusters), int(num_classes), assign.device
+        shaped = 1 <= Cc <= 1024 and 1 <= L <= 1024          # (the call itself rejects the rest, before any launch)
+        table = torch.empty((Cc, L) if shaped else (1, 1), dtype=torch.int64, device=dev)
+        dropped = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.check(self.lib.rsp_contingency(_ptr(assign), _ptr(y), assign.numel(), Cc, L, _ptr(table), _ptr(dropped), _stream()),
+                   "rsp_contingency")
+        return table, dropped
 
     # ---- fine-tune criterion, accuracy and meters (classify.hip) -------------------------------------------------
     def xent_metrics(self, logits, target, n_crop: int = 1, valid: Optional[int] = None, want_grad: bool = True, meters=None):

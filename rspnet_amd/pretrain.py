@@ -22,7 +22,7 @@ from pathlib import Path
 
 import torch
 
-from . import _lib, fingerprint, knn, linear_probe, ops, repr_stats
+from . import _lib, cluster, fingerprint, knn, linear_probe, ops, repr_stats
 from .framework.arguments import RUN_DIR_NAME_REGEX, add_driver_arguments, parse_driver_args, save_run_files  # noqa: F401
 from .framework.driver import (append_scalars, finish_process_group, init_process_group, launch, load_config, load_states, save_run,
                                seed_everything, setup_logging, visible_gpu_count)
@@ -192,6 +192,13 @@ class Engine:
         self.probe_loaders, self._probe_result = None, None
         if self.probe is not None and local_rank == 0:
             self.probe_loaders = self.probe.build_loaders(T, size, self.device, seed=args.seed)
+        # opt-in (config key "cluster_monitor", e.g. -x '{"cluster_monitor": {"every": 10, "num_clusters": 101, "num_classes": 101}}'):
+        # None otherwise.  Rank 0 clusters the bank's features (the kNN monitor's stand-in bank loader, its own instance) and scores
+        # the clusters against the labels
+        self.cluster = cluster.ClusterMonitor.from_config(cfg, self.num_epochs)
+        self.cluster_loader, self._cluster_result = None, None
+        if self.cluster is not None and local_rank == 0:
+            self.cluster_loader = self.cluster.build_loader(T, size, self.device, seed=args.seed)
 
     # ---- checkpoints (pretrain.py:112-132) ---------------------------------------------------------------------------
     def load_checkpoint(self, path):
@@ -282,6 +289,9 @@ class Engine:
             rec.update(self._repr_result)
         if self._probe_result is not None:
             rec.update({f"probe_{k}": self._probe_result[k] for k in ("acc1", "acc5", "loss")})
+        cl = getattr(self, "_cluster_result", None)      # (a stand-in engine of the driver tests may not carry it)
+        if cl is not None:
+            rec.update({f"cluster_{k}": cl[k] for k in ("nmi", "ari", "purity", "objective", "iters", "empty")})
         append_scalars(self.scalars_path, rec)
 
     def _run_knn_monitor(self):
@@ -341,6 +351,21 @@ class Engine:
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             torch.distributed.barrier()
 
+    def _run_cluster_monitor(self):
+        """After the other monitors and before the epoch's scalar line: rank 0 extracts, clusters and scores eagerly on the current
+        stream (nothing here is captured); the other ranks wait at a barrier.  Has run on one GPU only."""
+        self._cluster_result = None
+        m = self.cluster
+        if m is None or not m.due(self.current_epoch):
+            return
+        if self.local_rank == 0:
+            r = self._cluster_result = m.run(self.model, self.cluster_loader)
+            logger.info(f"Cluster [{self.current_epoch}/{self.num_epochs}]\tNMI {r['nmi']:.4f}\tARI {r['ari']:.4f}\tpurity {r['purity']:.4f}"
+                        f"\tobjective {r['objective']:.4f}\t({m.num_clusters} clusters, {r['iters']} iterations, {r['empty']} empty, "
+                        f"bank {r['n_bank']}, {r['bad_rows']} bad, {r['seconds']:.1f} s)")
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            torch.distributed.barrier()
+
     def run(self):
         num_epochs = 1 if self.args.debug else self.num_epochs
         self._first_epoch = self.current_epoch
@@ -358,6 +383,7 @@ class Engine:
             self._run_knn_monitor()
             self._run_repr_monitor()
             self._run_probe_monitor()
+            self._run_cluster_monitor()
             self.scheduler.step()
             self._write_scalars(lr)
             self.current_epoch += 1

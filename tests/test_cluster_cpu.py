@@ -1,0 +1,355 @@
+"""CPU: the clustering module's torch composition (cluster._kmeans_torch) against its definition (kmeans_reference), the conditions the
+test inputs were chosen for, the scores against closed forms and sklearn, the limits, the argument checks of the entry points, the
+monitor's configuration, the driver wiring and the command-line tool."""
+import ctypes
+import json
+import random
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import cluster_util as cu
+from cpu_ops import CpuOps
+from knn_util import feats
+from rspnet_amd import _lib, cluster, ops
+
+
+@pytest.fixture()
+def cpu_backend():
+    prev = ops.set_backend(CpuOps())      # has no kmeans_fit: cluster.fit_raw composes the rule from torch ops
+    yield
+    ops.set_backend(prev)
+
+
+def t(a):
+    return torch.from_numpy(np.array(a))
+
+
+# ---- the conditions on the inputs, from the fp64 reference alone -------------------------------------------------------------
+def test_step_cases_cover_the_grid_and_have_no_near_ties():
+    for i, values in enumerate(({1, 63, 64, 65, 129, 257}, {1, 2, 5, 101, 128, 129, 300, 1024}, {2, 30, 34, 200})):
+        seen = [c[i] for c in cu.STEP_CASES]
+        assert set(seen) == values and all(seen.count(v) >= 2 for v in values), (i, seen)
+    for case in cu.STEP_CASES:
+        cu.assert_step_conditions(case)
+
+
+@pytest.mark.parametrize("case", cu.EXACT_FITS, ids=str)
+def test_exact_fits_keep_their_gaps(case):
+    cu.assert_exact_conditions(case)
+
+
+@pytest.mark.parametrize("case", cu.FORCED_FITS, ids=str)
+def test_forced_fits_have_few_near_ties(case):
+    cu.assert_forced_conditions(case)
+
+
+def test_empty_case_leaves_324_clusters_empty():
+    x, _, cent = cu.empty_inputs()
+    ref = cluster.kmeans_reference(x, cent, 1)
+    assert ref.info["empty"] == 324 and (ref.counts[700:] == 0).all() and ref.info["iters_run"] == 1 and ref.info["converged"] == 0
+
+
+# ---- the torch composition -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", cu.STEP_CASES, ids=str)
+def test_torch_iteration_matches_reference(case, cpu_backend):
+    x, _, cent = cu.step_inputs(case)
+    res = cluster.fit_raw(t(x), t(cent), 1)
+    a2, sim = cluster.assign(t(cent), t(x))
+    assert torch.equal(a2, res.assign)
+    assert res.info == {"rows_valid": case[0], "rows_bad": 0, "iters_run": 1, "converged": 0, "empty": int((res.counts == 0).sum()),
+                        "unassigned": 0}
+    assert int(res.changed[0]) == case[0]
+    cu.check_iteration(x, cent, cu.step_reference(case)[0], res.assign.numpy(), sim.numpy(), res.counts.numpy(), res.cent.numpy(),
+                       float(res.objective[0]), f"torch {case}")
+
+
+@pytest.mark.parametrize("case", cu.EXACT_FITS, ids=str)
+def test_torch_fit_reproduces_the_reference(case, cpu_backend):
+    x, _, init = cu.exact_inputs(case)
+    ref = cu.exact_reference(case)
+    res = cluster.fit_raw(t(x), t(init), case[5] + 4)
+    assert res.info == ref.info
+    assert np.array_equal(res.changed.numpy(), ref.changed) and np.array_equal(res.assign.numpy(), ref.assign)
+    assert np.array_equal(res.counts.numpy(), ref.counts)
+    cu.check_trace_tail(res.changed.numpy(), res.objective.numpy(), ref.info["iters_run"])
+    assert np.allclose(res.objective.numpy()[:case[5]], ref.objective[:case[5]], atol=cu.SIM_TOL, rtol=0)
+
+
+def test_invalid_rows_and_unreturnable_centroids(cpu_backend):
+    x, _ = feats(3, 200, 34, 5, 1.0)
+    x = np.array(x)
+    bad = [0, 63, 64]
+    x[0] = 0
+    x[63, 33] = np.nan
+    x[64, 0] = np.inf
+    init = x[[5, 50, 100, 150]].copy()
+    ref = cluster.kmeans_reference(x, init, 30)
+    got = cluster.fit_raw(t(x), t(init), 30)
+    clean = cluster.fit_raw(t(np.delete(x, bad, axis=0)), t(init), 30)
+    assert got.info == ref.info and got.info["rows_bad"] == 3 and got.assign[bad].tolist() == [-1, -1, -1]
+    assert torch.equal(got.cent, clean.cent) and torch.equal(got.changed, clean.changed)
+    assert np.array_equal(np.delete(got.assign.numpy(), bad), clean.assign.numpy())
+    # a NaN centroid is never assigned; with nothing returnable every valid row is unassigned and nothing moves
+    cent = init.copy()
+    cent[1, 3] = np.nan
+    one = cluster.fit_raw(t(x), t(cent), 1)
+    assert not bool((one.assign == 1).any()) and one.info["unassigned"] == 0 and int(one.counts[1]) == 0
+    assert bool(torch.isnan(one.cent[1, 3]))
+    none = cluster.fit_raw(t(x), torch.full((4, 34), float("nan")), 3)
+    assert none.info == {"rows_valid": 197, "rows_bad": 3, "iters_run": 2, "converged": 1, "empty": 4, "unassigned": 197}
+    assert bool((none.assign == -1).all()) and none.changed.tolist() == [197, 0, -1] and float(none.objective[0]) == 0.0
+    ref_none = cluster.kmeans_reference(x, np.full((4, 34), np.nan), 3)
+    assert ref_none.info == none.info
+
+
+def test_fit_draws_distinct_valid_rows_with_its_own_generator(cpu_backend):
+    x, _ = feats(9, 120, 30, 4, 1.0)
+    x = np.array(x)
+    x[:100] = 0                                           # twenty valid rows
+    states = (random.getstate(), torch.get_rng_state().clone(), np.random.get_state()[1].copy())
+    a = cluster.fit(t(x), 20, max_iters=1, seed=3)
+    assert random.getstate() == states[0] and torch.equal(torch.get_rng_state(), states[1])
+    assert np.array_equal(np.random.get_state()[1], states[2])
+    assert a.info["rows_valid"] == 20 and a.counts.tolist() == [1] * 20      # every valid row is a centroid: distinct rows
+    b = cluster.fit(t(x), 20, max_iters=1, seed=3)
+    assert torch.equal(a.cent, b.cent) and torch.equal(a.assign, b.assign)
+    with pytest.raises(ValueError, match="valid rows"):
+        cluster.fit(t(x), 21)
+    x2, _ = feats(2, 300, 34, 6, 1.0)
+    one = cluster.fit(t(x2), 6, seed=1)
+    many = cluster.fit(t(x2), 6, seed=1, restarts=4)
+    last = lambda r: float(r.objective[r.info["iters_run"] - 1])
+    assert last(many) >= last(one)                        # the first draw of the four is the single fit's
+    init = t(x2[:6])
+    assert torch.equal(cluster.fit(t(x2), 6, init=init).cent, cluster.fit_raw(t(x2), init.clone(), 50).cent)
+
+
+# ---- scores --------------------------------------------------------------------------------------------------------------------
+def test_scores_closed_forms():
+    y = np.random.default_rng(0).integers(0, 7, 500)
+    table = np.zeros((7, 7), dtype=np.int64)
+    np.add.at(table, (y, y), 1)
+    s = cluster.scores(table)
+    assert s["nmi"] == pytest.approx(1.0, abs=1e-12) and s["ari"] == 1.0 and s["purity"] == 1.0 and s["n"] == 500
+    perm = np.random.default_rng(1).permutation(7)
+    p = cluster.scores(table[perm][:, np.random.default_rng(2).permutation(7)])
+    assert p["nmi"] == pytest.approx(1.0, abs=1e-12) and p["ari"] == 1.0 and p["purity"] == 1.0
+    one = cluster.scores(table.sum(axis=0, keepdims=True))            # a one-cluster fit
+    assert one["nmi"] == 0.0 and one["ari"] == 0.0 and one["purity"] == pytest.approx(np.bincount(y).max() / 500)
+    assert one["size_entropy"] == 0.0
+    rnd = np.random.default_rng(3).integers(0, 30, (9, 5))
+    a, b = cluster.scores(rnd), cluster.scores(rnd[np.random.default_rng(4).permutation(9)][:, np.random.default_rng(5).permutation(5)])
+    for k in ("nmi", "ari", "purity", "size_entropy"):
+        assert a[k] == pytest.approx(b[k], abs=1e-12), k
+    even = cluster.scores(np.full((4, 3), 5))
+    assert even["size_entropy"] == pytest.approx(1.0) and even["nmi"] == pytest.approx(0.0, abs=1e-12)
+    assert cluster.scores(np.zeros((3, 3), dtype=np.int64)) == {"n": 0, "nmi": 0.0, "ari": 0.0, "purity": 0.0, "size_entropy": 0.0}
+    assert cluster.scores(np.array([[4]]))["nmi"] == 1.0
+    try:
+        import scipy.optimize  # noqa: F401
+    except ImportError:
+        assert "hungarian_acc" not in s
+    else:
+        assert p["hungarian_acc"] == 1.0 and one["hungarian_acc"] == pytest.approx(np.bincount(y).max() / 500)
+
+
+def test_scores_against_sklearn():
+    metrics = pytest.importorskip("sklearn.metrics")
+    rng = np.random.default_rng(11)
+    for C, L, n in ((5, 5, 300), (12, 7, 1000), (1, 4, 50), (6, 1, 80), (101, 101, 3000)):
+        a, y = rng.integers(0, C, n), rng.integers(0, L, n)
+        if C == L:
+            a = np.where(rng.random(n) < 0.6, y, a)
+        table = np.zeros((C, L), dtype=np.int64)
+        np.add.at(table, (a, y), 1)
+        s = cluster.scores(table)
+        assert s["nmi"] == pytest.approx(metrics.normalized_mutual_info_score(y, a), abs=1e-12), (C, L)
+        assert s["ari"] == pytest.approx(metrics.adjusted_rand_score(y, a), abs=1e-12), (C, L)
+
+
+def test_contingency_composition(cpu_backend):
+    rng = np.random.default_rng(5)
+    a, y = rng.integers(-1, 6, 400), rng.integers(-1, 8, 400)
+    table, dropped = cluster.contingency(t(a.astype(np.int32)), t(y), 6, 7)
+    keep = (a >= 0) & (y >= 0) & (y < 7)
+    want = np.zeros((6, 7), dtype=np.int64)
+    np.add.at(want, (a[keep], y[keep]), 1)
+    assert np.array_equal(table.numpy(), want) and int(dropped) == int((~keep).sum())
+
+
+def test_evaluate_on_separated_classes(cpu_backend):
+    x, y = feats(7, 400, 34, 4, 6.0)
+    init = np.stack([x[y == c][0] for c in range(4)])
+    res = cluster.evaluate(t(x), t(y), 4, init=t(init))
+    assert res["nmi"] == pytest.approx(1.0, abs=1e-12) and res["ari"] == 1.0 and res["purity"] == 1.0 and res["empty"] == 0
+    assert res["converged"] == 1 and res["dropped"] == 0 and res["n"] == 400 and 0 < res["objective"] <= 1
+
+
+# ---- limits, arguments, configuration ------------------------------------------------------------------------------------------
+def test_limits_raise_value_error(cpu_backend):
+    x = torch.ones(8, 4)
+    for kw in (dict(num_clusters=0), dict(num_clusters=1025), dict(max_iters=0), dict(max_iters=1001), dict(restarts=0)):
+        args = dict(num_clusters=3)
+        args.update(kw)
+        with pytest.raises(ValueError, match="cluster"):
+            cluster.fit(x, **args)
+    for bad in (torch.zeros(8, 3), torch.zeros(8, 4098), torch.zeros(0, 4)):
+        with pytest.raises(ValueError, match="cluster"):
+            cluster.fit(bad, 3)
+    with pytest.raises(ValueError, match="cluster"):
+        cluster.check_limits(262145, 4, 3)
+    for L in (0, 1025):
+        with pytest.raises(ValueError, match="num_classes"):
+            cluster.contingency(torch.zeros(4, dtype=torch.int32), torch.zeros(4, dtype=torch.int64), 3, L)
+    with pytest.raises(ValueError, match="init"):
+        cluster.fit(x, 3, init=torch.ones(2, 4))
+
+
+def test_argument_checks_of_the_entry_points():
+    """RSP_EINVAL / RSP_EWORKSPACE with the entry point's name, on dummy pointers: nothing is dereferenced, nothing is launched."""
+    lib = _lib.load()
+    P, ODD = ctypes.c_void_p(1 << 20), ctypes.c_void_p((1 << 20) + 4)
+
+    def fit(x=P, ld=64, N=100, D=64, cent=P, C=7, iters=3, assign=P, obj=P, info=P, wsb=1 << 30):
+        return lib.rsp_kmeans_fit(x, ld, N, D, cent, C, iters, assign, P, P, obj, info, P, wsb, None)
+    for kw, what in ((dict(C=0), b"bad size"), (dict(C=1025), b"bad size"), (dict(N=0), b"bad size"), (dict(N=262145), b"bad size"),
+                     (dict(D=63), b"bad size"), (dict(D=4098, ld=4098), b"bad size"), (dict(D=0, ld=0), b"bad size"), (dict(ld=62), b"bad size"),
+                     (dict(ld=65), b"bad size"), (dict(iters=0), b"max_iters"), (dict(iters=1001), b"max_iters"),
+                     (dict(x=ODD), b"8-byte aligned"), (dict(cent=ODD), b"8-byte aligned"), (dict(obj=ODD), b"8-byte aligned"),
+                     (dict(info=ODD), b"8-byte aligned"), (dict(assign=None), b"null pointer"), (dict(info=None), b"null pointer")):
+        assert fit(**kw) == -1, kw
+        err = lib.rsp_last_error()
+        assert err.startswith(b"rsp_kmeans_fit: ") and what in err, (kw, err)
+    need = lib.rsp_kmeans_workspace(100, 64, 7)
+    assert need > 0 and fit(wsb=need - 1) == -2 and lib.rsp_last_error() == b"rsp_kmeans_fit: workspace too small"
+    for bad in ((0, 64, 7), (262145, 64, 7), (100, 63, 7), (100, 4098, 7), (100, 64, 0), (100, 64, 1025)):
+        assert lib.rsp_kmeans_workspace(*bad) == 0, bad
+
+    def assign(x=P, ld=64, D=64, C=7, out=P, sim=P, wsb=1 << 30):
+        return lib.rsp_kmeans_assign(x, ld, 100, D, P, C, out, sim, P, wsb, None)
+    for kw, what in ((dict(C=0), b"bad size"), (dict(D=66), b"bad size"), (dict(x=ODD), b"8-byte aligned"), (dict(out=None), b"null pointer")):
+        assert assign(**kw) == -1, kw
+        err = lib.rsp_last_error()
+        assert err.startswith(b"rsp_kmeans_assign: ") and what in err, (kw, err)
+    need = lib.rsp_cosine_topk_workspace(100, 7, 64, 1, 0)
+    assert assign(wsb=need - 1) == -2 and lib.rsp_last_error() == b"rsp_kmeans_assign: workspace too small"
+    assert need <= lib.rsp_kmeans_workspace(100, 64, 7)
+
+    def table(a=P, y=P, N=100, C=7, L=5, tab=P, dropped=P):
+        return lib.rsp_contingency(a, y, N, C, L, tab, dropped, None)
+    for kw, what in ((dict(N=0), b"bad size"), (dict(C=0), b"bad size"), (dict(C=1025), b"bad size"), (dict(L=0), b"bad size"),
+                     (dict(L=1025), b"bad size"), (dict(y=ODD), b"8-byte"), (dict(tab=ODD), b"8-byte"), (dict(dropped=None), b"null pointer")):
+        assert table(**kw) == -1, kw
+        err = lib.rsp_last_error()
+        assert err.startswith(b"rsp_contingency: ") and what in err, (kw, err)
+    assert lib.rsp_version() == 130 and ctypes.sizeof(_lib.KmeansInfo) == 32
+
+
+def test_workspace_is_the_stated_formula():
+    """The search's workspace (rsp_cosine_topk_workspace at k = 1), 256 bytes of state, the row list (4 N), 16 bytes per 256 rows, and
+    the split partials of cent and counts, each rounded up to 256 bytes.  splits = min(ceil(1024 / (ceil(C / 64) ceil(D / 128))),
+    ceil(N / 32) // 4), at least 1."""
+    lib = _lib.load()
+    up = lambda v: -(-v // 256) * 256
+    for N, D, C in ((9537, 512, 101), (16384, 128, 256), (129, 34, 7), (1, 2, 1), (262144, 4096, 1024)):
+        splits = max(1, min(-(-1024 // (-(-C // 64) * -(-D // 128))), -(-N // 32) // 4))
+        want = (up(lib.rsp_cosine_topk_workspace(N, C, D, 1, 0)) + 256 + up(4 * N) + up(16 * -(-N // 256)) + up(4 * splits * C * D)
+                + up(4 * splits * C))
+        assert lib.rsp_kmeans_workspace(N, D, C) == want, (N, D, C)
+
+
+def test_monitor_from_config_and_schedule():
+    assert cluster.ClusterMonitor.from_config({}, 10) is None
+    assert cluster.ClusterMonitor.from_config({"cluster_monitor": {"every": 0, "num_clusters": 5}}, 10) is None
+    m = cluster.ClusterMonitor.from_config({"cluster_monitor": {"every": 4, "num_clusters": 11, "num_classes": 9, "encoder": "k",
+                                                                "bank_samples": 96, "batch_size": 8, "n_crop": 2, "max_iters": 30,
+                                                                "seed": 5, "restarts": 3}}, 10)
+    assert (m.every, m.num_clusters, m.num_classes, m.encoder, m.bank_samples, m.batch_size, m.n_crop, m.max_iters, m.seed, m.restarts) == \
+        (4, 11, 9, "k", 96, 8, 2, 30, 5, 3)
+    assert [e for e in range(10) if m.due(e)] == [3, 7, 9]
+    with pytest.raises(ValueError, match="unknown keys"):
+        cluster.ClusterMonitor.from_config({"cluster_monitor": {"every": 1, "k": 5}}, 10)
+    for kw in (dict(encoder="x"), dict(num_clusters=0), dict(num_clusters=1025), dict(num_classes=0), dict(max_iters=0), dict(bank_samples=0),
+               dict(restarts=0), dict(num_clusters=300, bank_samples=256)):
+        with pytest.raises(ValueError):
+            cluster.ClusterMonitor(every=1, num_epochs=1, **kw)
+
+
+def test_pretext_configs_do_not_carry_the_key():
+    import glob
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    paths = glob.glob(os.path.join(root, "rspnet_amd", "config", "pretrain", "*.json"))
+    assert paths and all("cluster_monitor" not in json.load(open(p)) for p in paths)
+
+
+def test_monitor_refuses_to_run_inside_a_capture(monkeypatch):
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    with pytest.raises(RuntimeError, match="capture"):
+        cluster.ClusterMonitor(every=1, num_epochs=1).run(None, [])
+
+
+def test_command_line_tool(cpu_backend, tmp_path, caplog):
+    x, y = feats(7, 400, 34, 4, 6.0)
+    x2, y2 = feats(8, 90, 34, 4, 6.0)
+    for split, X, lab in (("train", x, y), ("test", x2, y2)):
+        np.save(tmp_path / f"{split}_fold2_feats.npy", X.astype(np.float64))
+        np.save(tmp_path / f"{split}_fold2_labels.npy", lab)
+    with caplog.at_level("INFO", logger="rspnet_amd.cluster"):
+        out = cluster.main(["--features", str(tmp_path), "--fold", "2", "--restarts", "3"])
+    with open(tmp_path / "cluster_fold2.json") as f:
+        saved = json.load(f)
+    assert saved == out and saved["clusters"] == 4 and saved["num_classes"] == 4 and saved["n"] == 400 and saved["split"] == "train"
+    assert 0 <= saved["ari"] <= saved["purity"] <= 1 and 0 <= saved["nmi"] <= 1 + 1e-12 and saved["bad_rows"] == 0
+    assert f"k-means C=4 on 400 train rows: NMI = {saved['nmi']:.4f}, ARI = {saved['ari']:.4f}" in caplog.text
+    out = cluster.main(["--features", str(tmp_path), "--fold", "2", "--split", "test", "--clusters", "6", "--iters", "7", "--seed", "2"])
+    assert (out["split"], out["clusters"], out["max_iters"], out["seed"], out["restarts"], out["n"]) == ("test", 6, 7, 2, 1, 90)
+    assert out["iters"] <= 7
+
+
+def test_pretext_driver_wiring_without_a_device(tmp_path):
+    """The driver's two methods on a stand-in engine (the driver itself binds to the device; its end-to-end run is a GPU test): the
+    monitor runs when due and only then, on rank 0 only, its six scalars go into that epoch's line and into no other, and the line's
+    other numbers are what they are without the monitor."""
+    from rspnet_amd.pretrain import Engine
+
+    class Mon:
+        num_clusters, calls = 5, []
+
+        def due(self, epoch):
+            return epoch % 2 == 1
+
+        def run(self, model, bank):
+            Mon.calls.append((model, bank))
+            return {"nmi": 0.5, "ari": 0.25, "purity": 0.75, "objective": 0.9, "iters": 7, "empty": 1, "n_bank": 24, "bad_rows": 0,
+                    "seconds": 0.1}
+
+    stats = {k: {"avg": float(i)} for i, k in enumerate(("loss", "loss_A", "acc1_A", "acc5_A", "loss_M", "acc1_M"))}
+
+    def engine(mon, rank=0, name="with"):
+        return types.SimpleNamespace(cluster=mon, cluster_loader="bank", _cluster_result=None, _probe_result=None, _knn_result=None,
+                                     _repr_result=None, local_rank=rank, current_epoch=0, num_epochs=2, model="model", stats=stats,
+                                     scalars_path=tmp_path / f"{name}.jsonl")
+    for name, mon in (("with", Mon()), ("without", None)):
+        e = engine(mon, name=name)
+        for epoch in range(2):
+            e.current_epoch = epoch
+            Engine._run_cluster_monitor(e)
+            Engine._write_scalars(e, 0.05)
+    lines = {name: [json.loads(l) for l in open(tmp_path / f"{name}.jsonl")] for name in ("with", "without")}
+    assert Mon.calls == [("model", "bank")]
+    first, second = lines["with"]
+    assert not any(k.startswith("cluster_") for k in first)
+    assert {k: v for k, v in second.items() if k.startswith("cluster_")} == {
+        "cluster_nmi": 0.5, "cluster_ari": 0.25, "cluster_purity": 0.75, "cluster_objective": 0.9, "cluster_iters": 7, "cluster_empty": 1}
+    assert not any(k.startswith("cluster_") for rec in lines["without"] for k in rec)
+    for a, b in zip(lines["with"], lines["without"]):
+        assert {k: v for k, v in a.items() if not k.startswith("cluster_")} == b
+    other = engine(Mon(), rank=1)
+    other.current_epoch = 1
+    Engine._run_cluster_monitor(other)
+    assert other._cluster_result is None and len(Mon.calls) == 1
