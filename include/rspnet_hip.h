@@ -799,6 +799,66 @@ int rsp_kmeans_assign(const float* x, int32_t ld, int32_t N, int32_t D, const fl
 int rsp_contingency(const int32_t* assign, const int64_t* y, int32_t N, int32_t C, int32_t L, int64_t* table /* [C][L] */,
                     int64_t* dropped /* [1] */, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Embedding maps (tsne.hip; the project's own, no counterpart in the reference): exact t-SNE of N stored feature rows.  The
+ * affinities are ONE call; all `iters` iterations of the descent are issued from ONE call, three launches each, nothing read back.
+ * Additive: the ABI version stays 130.
+ * x: N x D fp32 row-major with row pitch ld; D and ld even, ld >= D, the base 8-byte aligned (the rule of the cosine search).
+ * 2 <= N <= 16384, 2 <= D <= 4096, perplexity finite and in [1, 1024], 1 <= iters <= 10000, 0 <= first_iter.
+ * pmat [N][ldp], ldp >= N (its top-left M x M holds p over the listed rows, the rest of the N x N is written as 0), dmat (optional,
+ * pmat's shape and pitch; without it the distances live in the workspace), rows [N] int32, beta [N]: 4-byte aligned.  y, inc, gains
+ * [N][2] fp32 indexed by the ORIGINAL row, kl_trace [iters] fp64, sched [first_iter + iters][4] fp32, info and both workspaces:
+ * 8-byte aligned.
+ *   valid rows   row i is valid iff its fp32 sum of squares ss_i, formed by rsp_row_sumsq -- the search's routine: each lane of a wave
+ *                its float2 columns 2 l, 2 l + 128, ... by fmaf, x then y; then the wave's xor butterfly --, is finite and > 0.  The
+ *                valid rows are listed once, in ascending order: rows[r] for rank r < M, -1 behind; M = info.rows_valid.  Every later
+ *                kernel walks that list, so an invalid row takes part in nothing, its y, inc and gains are never read or written, and
+ *                the result equals, to the bit, the result on x without that row.
+ *   distance     s_ij = (x_i . x_j) * inv_i * inv_j in fp32 on the fp32 MFMA (a k-ordered chain; inv = 1 / sqrtf(ss)), the inverse
+ *                norm of the lower rank applied first: the search's expression above the diagonal, its mirror image below.
+ *                d_ij = fmaxf(2 - 2 s_ij, 0); d_ii is not used (stored as 0); d is symmetric to the bit.
+ *   calibration  per rank i over j != i: m_i = min_j d_ij; e_j(b) = expf(-b (d_ij - m_i)), S = sum e_j, A = sum e_j (d_ij - m_i) (fmaf),
+ *                H = logf(S) + b A / S.  b = 1, lo = 0, hi = +inf, then exactly 64 steps: H > logf(perplexity): lo = b, b = isinf(hi) ?
+ *                2 b : (lo + hi) / 2; otherwise hi = b, b = (lo + hi) / 2.  No early exit.  beta[r] = the final b, NaN for r >= M;
+ *                c_ij = e_j(beta_i) / S_i with S_i formed at the final b.  Every row sum: lane l of one wave adds columns l, l + 64, ...
+ *                in ascending order in fp32, then the xor butterfly.  No atomics.
+ *   joint        p_ij = (c_ij + c_ji) * (1 / (2 M)) in fp32, the lower rank's term first; p_ii = 0; symmetric to the bit.  c_ji is
+ *                recomputed from d_ij (= d_ji) and rank j's (beta, m, S), so it is the same float the calibration of j defines.
+ *                info.psum = sum p, info.plogp = sum over p > 0 of p logf(p) (the fp32 product), added in fp64: thread t of rank i's
+ *                block adds columns t, t + 256, ...; the wave butterfly, the four waves in order; then the ranks t, t + 1024, ... of
+ *                one block, the butterfly, the sixteen waves in order.
+ *   iteration t  over listed i != j: r2 = dx dx + dy dy with (dx, dy) = y_i - y_j, w = 1 / (1 + r2); attr_i = sum p_ij w (dx, dy),
+ *                rep_i = sum w w (dx, dy), z_i = sum w, e_i = sum p_ij log1pf(r2); Z = sum z_i, E = sum e_i;
+ *                g_i = 4 (exag_t attr_i - rep_i / (float)Z); kl_trace[t] = plogp + E + log(Z): the KL of the map BEFORE the update,
+ *                with the un-exaggerated p.  Per coordinate: gains = ((g > 0) != (inc > 0)) ? gains + 0.2 : gains * 0.8, floored at
+ *                0.01; inc = mom_t inc - lr_t gains g; y += inc.  No re-centring.  (lr_t, mom_t, exag_t, pad) = sched[first_iter + t].
+ *   order        the ranks j are cut into 64-column chunks and the chunks into `splits` ranges (splits from M alone).  Thread (wave
+ *                w, lane r) of a block takes rank i0 + r and columns 16 w .. 16 w + 15 of every chunk of the range in ascending order
+ *                in fp32; the four waves are added in wave order, the ranges in range order (fp32).  Z and E: the z_i, e_i of 256
+ *                ranks in fp64 by the butterfly and the four waves in order; those blocks lane l: l, l + 64, ..., then the butterfly.
+ *                No atomics, no memset, no memcpy: the same input gives the same bits, eagerly or replayed.
+ *   non-finite   a NaN or Inf in x invalidates that row only; one in y, inc, gains or sched propagates as the arithmetic says (Z goes
+ *                NaN, then the whole map and kl_trace from that iteration on).
+ * rsp_tsne_fit takes pmat, rows and info as rsp_tsne_affinities left them (N: the same N); it is resumable: a second call with
+ * first_iter advanced continues the same trajectory.
+ * A bad argument is RSP_EINVAL with the entry point's name in rsp_last_error(), a workspace below the query RSP_EWORKSPACE, both
+ * before anything is launched.  Kernels only, all on `stream`; capturable after a first eager call.
+ * workspaces: affinities -- the state, four vectors of N floats, 2 N doubles and the N x N distances; fit -- the split partials
+ * (splits x N x 8 floats), 4 N floats and the block partials, each rounded up to 256 bytes.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct rsp_tsne_info {      /* device struct, 32 bytes */
+  double plogp, psum;
+  int64_t rows_valid, rows_bad;
+} rsp_tsne_info;
+size_t rsp_tsne_affinities_workspace(int32_t N, int32_t D);
+int rsp_tsne_affinities(const float* x, int32_t ld, int32_t N, int32_t D, float perplexity, float* pmat, int32_t ldp,
+                        int32_t* rows /* [N] */, float* beta /* [N] */, float* dmat /* nullable */, rsp_tsne_info* info,
+                        void* workspace, size_t workspace_bytes, void* stream);
+size_t rsp_tsne_fit_workspace(int32_t N);
+int rsp_tsne_fit(const float* pmat, int32_t ldp, const int32_t* rows, const rsp_tsne_info* info, int32_t N, const float* sched_dev,
+                 int32_t first_iter, int32_t iters, float* y, float* inc, float* gains, double* kl_trace /* [iters] */,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

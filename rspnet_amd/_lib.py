@@ -86,6 +86,11 @@ class KmeansInfo(C.Structure):
                 ("empty", C.c_int32), ("unassigned", C.c_int32)]
 
 
+class TsneInfo(C.Structure):
+    """rsp_tsne_info (32 bytes)"""
+    _fields_ = [("plogp", C.c_double), ("psum", C.c_double), ("rows_valid", C.c_int64), ("rows_bad", C.c_int64)]
+
+
 _PD = C.POINTER(ConvDesc)
 _PP = C.POINTER(PoolDesc)
 _sz = C.c_size_t
@@ -196,6 +201,10 @@ SIGNATURES = {
     "rsp_kmeans_fit": (C.c_int, [_p, _i32, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "rsp_kmeans_assign": (C.c_int, [_p, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _sz, _p]),
     "rsp_contingency": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p]),
+    "rsp_tsne_affinities_workspace": (_sz, [_i32, _i32]),
+    "rsp_tsne_affinities": (C.c_int, [_p, _i32, _i32, _i32, _f, _p, _i32, _p, _p, _p, _p, _p, _sz, _p]),
+    "rsp_tsne_fit_workspace": (_sz, [_i32]),
+    "rsp_tsne_fit": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

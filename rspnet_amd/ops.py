@@ -202,6 +202,7 @@ def _dy_target(y, in_ld: int, dy_out):
 KnnResult = collections.namedtuple("KnnResult", "pred rank hits votes idx dist")      # of HipOps.knn_classify
 ReprResult = collections.namedtuple("ReprResult", "sums gram colsum")                  # of HipOps.repr_stats
 KmeansResult = collections.namedtuple("KmeansResult", "assign counts changed objective info")      # of HipOps.kmeans_fit
+TsneAffinities = collections.namedtuple("TsneAffinities", "pmat rows beta dmat info")                  # of HipOps.tsne_affinities
 
 
 class HipOps:
@@ -983,6 +984,50 @@ class HipOps:
         _lib.check(self.lib.rsp_contingency(_ptr(assign), _ptr(y), assign.numel(), Cc, L, _ptr(table), _ptr(dropped), _stream()),
                    "rsp_contingency")
         return table, dropped
+
+    # ---- embedding maps (tsne.hip) ----------------------------------------------------------------------------------------
+    def tsne_affinities(self, x, perplexity: float = 30.0, want_dmat: bool = False):
+        """The joint t-SNE affinities of the rows of x (N, D) from one rsp_tsne_affinities call (include/rspnet_hip.h states the
+        rule).  Returns the named tuple (pmat fp32 (N, N): p over the M listed rows in its top-left M x M, 0 elsewhere; rows int32
+        (N,): the valid rows in ascending order, -1 behind; beta fp32 (N,) by rank, NaN behind; dmat fp32 (N, N) | None; info: the
+        32-byte rsp_tsne_info as a uint8 device tensor).  Rows of x may be strided (unit column stride, even row pitch)."""
+        N, D, ld = self._probe_x("tsne_affinities", x)
+        dev = x.device
+        shaped = 2 <= N <= 16384          # (the call itself rejects the rest, before any launch)
+        n = N if shaped else 1
+        pmat = torch.empty((n, n), dtype=torch.float32, device=dev)
+        rows = torch.empty(n, dtype=torch.int32, device=dev)
+        beta = torch.empty(n, dtype=torch.float32, device=dev)
+        dmat = torch.empty((n, n), dtype=torch.float32, device=dev) if want_dmat else None
+        info = torch.empty(C.sizeof(_lib.TsneInfo), dtype=torch.uint8, device=dev)
+        wsb = int(self.lib.rsp_tsne_affinities_workspace(N, D))      # (0 for sizes the call itself rejects)
+        ws = self._workspace(dev, wsb)
+        _lib.check(self.lib.rsp_tsne_affinities(_ptr(x), ld, N, D, float(perplexity), _ptr(pmat), n, _ptr(rows), _ptr(beta), _ptr(dmat),
+                                                _ptr(info), _ptr(ws), wsb, _stream()), "rsp_tsne_affinities")
+        return TsneAffinities(pmat, rows, beta, dmat, info)
+
+    def tsne_fit(self, aff, sched, first_iter: int, iters: int, y, inc, gains):
+        """``iters`` iterations of the t-SNE descent on the affinities ``aff`` (of tsne_affinities), all from one rsp_tsne_fit call.
+        y, inc and gains (N, 2) fp32 are updated in place (the rows that are not listed are neither read nor written); sched
+        (>= first_iter + iters, 4) fp32 on the device: lr, momentum, exaggeration and a pad word per iteration.  Returns kl_trace
+        fp64 (iters,)."""
+        N = aff.pmat.shape[0]
+        for n, t in (("pmat", aff.pmat), ("sched", sched), ("y", y), ("inc", inc), ("gains", gains)):
+            _chk(t, n)
+        _chk(aff.rows, "rows", torch.int32)
+        iters, first_iter = int(iters), int(first_iter)
+        if any(tuple(t.shape) != (N, 2) for t in (y, inc, gains)) or sched.dim() != 2 or sched.shape[1] != 4:
+            raise _lib.RspError(f"tsne_fit: y {tuple(y.shape)}, inc {tuple(inc.shape)}, gains {tuple(gains.shape)} must be ({N}, 2), "
+                                f"sched {tuple(sched.shape)} (iterations, 4)")
+        if iters >= 1 and first_iter >= 0 and sched.shape[0] < first_iter + iters:
+            raise _lib.RspError(f"tsne_fit: {sched.shape[0]} schedule entries for iterations up to {first_iter + iters}")
+        dev = y.device
+        kl = torch.empty(max(iters, 1), dtype=torch.float64, device=dev)
+        wsb = int(self.lib.rsp_tsne_fit_workspace(N))
+        ws = self._workspace(dev, wsb)
+        _lib.check(self.lib.rsp_tsne_fit(_ptr(aff.pmat), aff.pmat.stride(0), _ptr(aff.rows), _ptr(aff.info), N, _ptr(sched), first_iter,
+                                         iters, _ptr(y), _ptr(inc), _ptr(gains), _ptr(kl), _ptr(ws), wsb, _stream()), "rsp_tsne_fit")
+        return kl[:iters]
 
     # ---- fine-tune criterion, accuracy and meters (classify.hip) -------------------------------------------------
     def xent_metrics(self, logits, target, n_crop: int = 1, valid: Optional[int] = None, want_grad: bool = True, meters=None):

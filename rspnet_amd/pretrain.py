@@ -22,7 +22,7 @@ from pathlib import Path
 
 import torch
 
-from . import _lib, cluster, fingerprint, knn, linear_probe, ops, repr_stats
+from . import _lib, cluster, fingerprint, knn, linear_probe, ops, repr_stats, tsne
 from .framework.arguments import RUN_DIR_NAME_REGEX, add_driver_arguments, parse_driver_args, save_run_files  # noqa: F401
 from .framework.driver import (append_scalars, finish_process_group, init_process_group, launch, load_config, load_states, save_run,
                                seed_everything, setup_logging, visible_gpu_count)
@@ -199,6 +199,13 @@ class Engine:
         self.cluster_loader, self._cluster_result = None, None
         if self.cluster is not None and local_rank == 0:
             self.cluster_loader = self.cluster.build_loader(T, size, self.device, seed=args.seed)
+        # opt-in (config key "tsne_monitor", e.g. -x '{"tsne_monitor": {"every": 10, "perplexity": 30, "iters": 500}}'): None
+        # otherwise.  Rank 0 maps the bank's features (the kNN monitor's stand-in bank loader, its own instance) with t-SNE and
+        # writes tsne_epoch{E}.png / .npy into the run directory
+        self.tsne = tsne.TsneMonitor.from_config(cfg, self.num_epochs)
+        self.tsne_loader, self._tsne_result = None, None
+        if self.tsne is not None and local_rank == 0:
+            self.tsne_loader = self.tsne.build_loader(T, size, self.device, seed=args.seed)
 
     # ---- checkpoints (pretrain.py:112-132) ---------------------------------------------------------------------------
     def load_checkpoint(self, path):
@@ -292,6 +299,9 @@ class Engine:
         cl = getattr(self, "_cluster_result", None)      # (a stand-in engine of the driver tests may not carry it)
         if cl is not None:
             rec.update({f"cluster_{k}": cl[k] for k in ("nmi", "ari", "purity", "objective", "iters", "empty")})
+        ts = getattr(self, "_tsne_result", None)
+        if ts is not None:
+            rec.update({"tsne_kl": ts["kl"], "tsne_purity": ts["purity"]})
         append_scalars(self.scalars_path, rec)
 
     def _run_knn_monitor(self):
@@ -366,6 +376,21 @@ class Engine:
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             torch.distributed.barrier()
 
+    def _run_tsne_monitor(self):
+        """After the other monitors and before the epoch's scalar line: rank 0 extracts and maps eagerly on the current stream (nothing
+        here is captured); the other ranks wait at a barrier.  Has run on one GPU only."""
+        self._tsne_result = None
+        m = getattr(self, "tsne", None)      # (a stand-in engine of the driver tests may not carry it)
+        if m is None or not m.due(self.current_epoch):
+            return
+        if self.local_rank == 0:
+            prefix = os.path.join(os.path.dirname(str(self.scalars_path)), f"tsne_epoch{self.current_epoch}")
+            r = self._tsne_result = m.run(self.model, self.tsne_loader, prefix)
+            logger.info(f"t-SNE [{self.current_epoch}/{self.num_epochs}]\tKL {r['kl']:.4f}\tpurity@10 {r['purity']:.4f}"
+                        f"\t(perplexity {m.perplexity:g}, {m.iters} iterations, bank {r['n_bank']}, {r['bad_rows']} bad, {r['seconds']:.1f} s)")
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            torch.distributed.barrier()
+
     def run(self):
         num_epochs = 1 if self.args.debug else self.num_epochs
         self._first_epoch = self.current_epoch
@@ -384,6 +409,7 @@ class Engine:
             self._run_repr_monitor()
             self._run_probe_monitor()
             self._run_cluster_monitor()
+            self._run_tsne_monitor()
             self.scheduler.step()
             self._write_scalars(lr)
             self.current_epoch += 1
