@@ -41,6 +41,8 @@ from torch import Tensor, nn
 from . import _lib
 from . import knn as _knn
 from . import ops as _ops
+from .framework.monitor import EpochMonitor
+from .knn import _rows, _valid_rows_np, _valid_rows_torch
 
 logger = logging.getLogger(__name__)
 MAX_ROWS, MAX_CLUSTERS, MAX_CLASSES, MAX_D, MAX_ITERS = 262144, 1024, 1024, 4096, 1000
@@ -68,12 +70,6 @@ def check_limits(N, D, num_clusters, max_iters=1, num_classes=1):
 
 
 # ---- the definition in numpy fp64 ----------------------------------------------------------------------------------------
-def _valid_rows_np(x32: np.ndarray) -> np.ndarray:
-    with np.errstate(all="ignore"):
-        ss = (x32 * x32).sum(axis=1, dtype=np.float32)
-        return np.isfinite(ss) & (ss > 0)
-
-
 def reference_similarities(x, cent) -> np.ndarray:
     """(N, C) fp64 similarities of the rule: -inf in the column of a centroid that holds a NaN or an Inf (never returned), NaN in
     the row of an invalid row."""
@@ -151,11 +147,6 @@ def kmeans_reference(x, init, max_iters: int) -> KMeansRef:
 
 
 # ---- the same rule from torch ops ----------------------------------------------------------------------------------------
-def _valid_rows_torch(x: Tensor) -> Tensor:
-    ss = (x * x).sum(dim=1)
-    return torch.isfinite(ss) & (ss > 0)
-
-
 def _assign_torch(x: Tensor, cent: Tensor):
     """(assign int32, sim fp32) of the rule from torch ops (this one stores the N x C matrix)."""
     ok = _valid_rows_torch(x)
@@ -207,13 +198,6 @@ def _contingency_torch(assign: Tensor, y: Tensor, C: int, L: int):
 
 
 # ---- the public calls ----------------------------------------------------------------------------------------------------
-def _rows(x: Tensor) -> Tensor:
-    x = x.to(torch.float32)
-    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) % 2):
-        x = x.contiguous()
-    return x
-
-
 def read_info(info: Tensor) -> dict:
     """The 32-byte rsp_kmeans_info of HipOps.kmeans_fit as a dict (one small copy to the host)."""
     rec = _lib.KmeansInfo.from_buffer_copy(info.cpu().numpy().tobytes())
@@ -350,20 +334,19 @@ def evaluate(x: Tensor, y: Tensor, num_clusters: int, num_classes: Optional[int]
 
 
 # ---- the pretext driver's hook -------------------------------------------------------------------------------------------
-class ClusterMonitor:
+class ClusterMonitor(EpochMonitor):
     """Every ``every``-th epoch (and on the last one): k-means on the backbone features of a labelled bank from one encoder of the
     pretext model (``knn.extract``), scored against the bank's labels.  ``run`` leaves the model as it found it -- state_dict() bit for
     bit, every module's ``training`` flag --, draws from no global random generator and refuses to run inside a graph capture.  Has
-    run on one GPU only."""
+    run on one GPU only.  Config, e.g. {"every": 10, "num_clusters": 101, "num_classes": 101}."""
 
+    KEY = "cluster_monitor"
     KEYS = ("every", "num_clusters", "num_classes", "encoder", "bank_samples", "batch_size", "n_crop", "max_iters", "seed", "restarts")
 
     def __init__(self, every: int, num_epochs: int, num_clusters: int = 101, num_classes: int = 101, encoder: str = "q",
                  bank_samples: int = 256, batch_size: int = 32, n_crop: int = 1, max_iters: int = 50, seed: int = 0, restarts: int = 1):
-        if encoder not in ("q", "k"):
-            raise ValueError(f"cluster_monitor: encoder must be 'q' or 'k', got {encoder!r}")
-        if int(every) < 1 or min(int(bank_samples), int(batch_size), int(n_crop), int(restarts)) < 1:
-            raise ValueError("cluster_monitor: every, bank_samples, batch_size, n_crop and restarts must be at least 1")
+        self._check_encoder(encoder)
+        self._check_at_least_1(every=every, bank_samples=bank_samples, batch_size=batch_size, n_crop=n_crop, restarts=restarts)
         check_limits(bank_samples, 2, num_clusters, max_iters, num_classes)
         if int(num_clusters) > int(bank_samples):
             raise ValueError(f"cluster_monitor: {num_clusters} clusters need at least as many bank samples, got {bank_samples}")
@@ -372,50 +355,29 @@ class ClusterMonitor:
         self.bank_samples, self.batch_size, self.n_crop = int(bank_samples), int(batch_size), int(n_crop)
         self.max_iters, self.seed, self.restarts = int(max_iters), int(seed), int(restarts)
 
-    @classmethod
-    def from_config(cls, cfg, num_epochs: int) -> Optional["ClusterMonitor"]:
-        """The ``cluster_monitor`` key of a pretext config, e.g. {"every": 10, "num_clusters": 101, "num_classes": 101}; None --
-        nothing constructed, no launch ever added -- when the key is absent or ``every`` is 0."""
-        node = cfg.get("cluster_monitor") if hasattr(cfg, "get") else None
-        if not node or int(node.get("every", 0)) <= 0:
-            return None
-        extra = sorted(set(node) - set(cls.KEYS))
-        if extra:
-            raise ValueError(f"cluster_monitor: unknown keys {extra}")
-        return cls(num_epochs=num_epochs, **{key: node[key] for key in cls.KEYS if key in node})
-
-    def due(self, epoch: int) -> bool:
-        """``epoch``: the 0-based epoch that has just finished its last step."""
-        return (int(epoch) + 1) % self.every == 0 or int(epoch) + 1 == self.num_epochs
-
-    def build_loader(self, T: int, size: int, device, seed: int = 0):
+    def build_loaders(self, T: int, size: int, device, seed: int = 0) -> tuple:
         """The kNN monitor's stand-in bank: split 'train' of ``SyntheticLabelledClips``."""
-        return _knn.synthetic_loaders(self.bank_samples, 1, self.batch_size, self.num_classes, self.n_crop, T, size, device, seed)[0]
+        return _knn.synthetic_loaders(self.bank_samples, 1, self.batch_size, self.num_classes, self.n_crop, T, size, device, seed)[:1]
 
     def run(self, model: nn.Module, bank_loader: Iterable) -> dict:
         """{"nmi", "ari", "purity", "objective", "iters", "empty", "n_bank", "bad_rows", "seconds"}."""
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("ClusterMonitor.run: never inside a graph capture")
+        self._refuse_capture()
         t0 = time.perf_counter()
-        net = getattr(model, "module", model)
-        enc = net.encoder_q if self.encoder == "q" else net.encoder_k
-        device = next(enc.parameters()).device
-        flags = [(m, m.training) for m in net.modules()]
-        try:
-            net.eval()
-            if self.encoder == "q" and hasattr(net, "_check_q_weights"):      # as knn.extract_bank_and_query
-                if not net._q_params:
-                    net._q_params = list(net.encoder_q.parameters())
-                net._check_q_weights()
-            n_crop = 1 if getattr(bank_loader, "split", None) == "train" else self.n_crop
-            g, y_g = _knn.extract(enc, bank_loader, device, n_crop)
-        finally:
-            for m, was in flags:
-                m.training = was
+        with _knn.frozen_encoder(model, self.encoder) as enc:
+            g, y_g = _knn.extract_bank(enc, bank_loader, self.n_crop)
         with torch.no_grad():
             res = evaluate(g, y_g, self.num_clusters, self.num_classes, self.max_iters, self.seed, restarts=self.restarts)
         return {"nmi": res["nmi"], "ari": res["ari"], "purity": res["purity"], "objective": res["objective"], "iters": res["iters"],
                 "empty": res["empty"], "n_bank": int(g.shape[0]), "bad_rows": res["bad_rows"], "seconds": time.perf_counter() - t0}
+
+    def scalars(self, result: dict) -> dict:
+        return {f"cluster_{k}": result[k] for k in ("nmi", "ari", "purity", "objective", "iters", "empty")}
+
+    def log_line(self, result: dict, ctx: dict) -> str:
+        r = result
+        return (f"Cluster [{ctx['epoch']}/{ctx['num_epochs']}]\tNMI {r['nmi']:.4f}\tARI {r['ari']:.4f}\tpurity {r['purity']:.4f}"
+                f"\tobjective {r['objective']:.4f}\t({self.num_clusters} clusters, {r['iters']} iterations, {r['empty']} empty, "
+                f"bank {r['n_bank']}, {r['bad_rows']} bad, {r['seconds']:.1f} s)")
 
 
 # ---- command line over saved retrieval features --------------------------------------------------------------------------

@@ -8,7 +8,7 @@
 //
 // Kernels (fit: six launches per iteration, every one of them returns at once while the stop flag of the state is set):
 //   km_compact_kernel   once per call, one block: the valid rows of x in ascending order as a list of row indices and their number
-//                       M (ballot + prefix counts, probe_compact_kernel's scheme); assign = -1 for the invalid ones; the state reset.
+//                       M (rsp_compact_rows, cos_search.h); assign = -1 for the invalid ones; the state reset.
 //                       Every later kernel walks that list by rank, so the fit is, to the bit, the fit on x without the invalid rows.
 //   km_assign_kernel    one thread per listed row: the search's k = 1 lists merged in split order (a later split's entry takes over
 //                       only when strictly greater: the tie rule), the new assignment against the previous one; a block of 256 ranks
@@ -53,26 +53,11 @@ __host__ __device__ __forceinline__ int km_splits(int cap, int rows) {
 
 __global__ __launch_bounds__(256) void km_compact_kernel(const float* __restrict__ inv, int N, int* __restrict__ rows,
                                                          int* __restrict__ assign, KmState* __restrict__ st) {
-  __shared__ int wcnt[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int base = 0;
-  for (int start = 0; start < N; start += 256) {
-    const int i = start + t;
-    const bool v = i < N && inv[i] > 0.f;      // (ss finite and > 0; a NaN fails the comparison)
-    const unsigned long long mask = __ballot(v);
-    if (lane == 0) wcnt[wave] = __popcll(mask);
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      woff += w < wave ? wcnt[w] : 0;
-      tot += wcnt[w];
-    }
-    if (v) rows[base + woff + __popcll(mask & ((1ull << lane) - 1ull))] = i;
-    if (i < N && !v) assign[i] = -1;
-    base += tot;
-    __syncthreads();
-  }
+  const int t = threadIdx.x;
+  const auto valid = [&](int i) { return inv[i] > 0.f; };      // (ss finite and > 0: rsp_inv_norms)
+  const int base = rsp_compact_rows(0, N, valid, [&](int r, int i) { rows[r] = i; });
+  for (int i = t; i < N; i += 256)
+    if (!valid(i)) assign[i] = -1;
   if (t == 0) {
     st->stop = 0;
     st->iters_run = 0;

@@ -65,6 +65,19 @@ int rsp_launch_lds(dim3 grid, size_t lds, size_t lds_max, hipStream_t s, const s
   return rsp_check_launch(fmt);
 }
 
+// The same launch without the note, for the kernels outside the convolution launchers (repr_stats.hip, linear_probe.hip: the note is
+// what rsp_last_conv_kernel reads): the attribute goes to `lds` on the instance's first launch, so a capture comes after one eager call.
+template <auto KERNEL, class... Args>
+int launch_lds(const char* name, dim3 grid, size_t lds, hipStream_t s, Args... args) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds, s, args...);
+  return rsp_check_launch(name);
+}
+
 #define RSP_REQUIRE(cond, msg)     \
   do {                             \
     if (!(cond)) {                 \

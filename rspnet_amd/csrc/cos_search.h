@@ -21,6 +21,39 @@ __device__ __forceinline__ float rsp_row_sumsq(const float* __restrict__ p, int 
   return rsp_wave_sum(s);
 }
 
+// inv[row] = 1 / sqrtf(rsp_row_sumsq(row)) for the n rows of x, 0 for a row whose sum of squares is not finite and > 0 (one launch of
+// inv_norm_kernel, cos_search.hip): the inverse norms of the search, and the validity flag of rsp_repr_stats, rsp_kmeans_fit and
+// rsp_tsne_affinities.  stop: nullptr, or a device flag that turns the launch into a no-op while it is not 0.
+int rsp_inv_norms(const float* x, int ld, int n, int D, float* inv, const int* stop, hipStream_t s);
+
+// Stream compaction of the indices [lo, hi) by a block of 256 threads, in trips of 256: emit(rank, i) for every i with valid(i), rank
+// counting the valid indices in ascending order from 0 (the wave's ballot, the four waves' counts through LDS, the trips' running
+// total: integers, order fixed).  Returns the number of valid indices to every thread.  Holds barriers: all 256 threads call it.
+// probe_compact_kernel (linear_probe.hip), km_compact_kernel (cluster.hip) and ts_compact_kernel (tsne.hip) are this plus a trailer.
+template <class Index, class Valid, class Emit>
+__device__ __forceinline__ int rsp_compact_rows(Index lo, Index hi, Valid valid, Emit emit) {
+  __shared__ int wcnt[4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  int base = 0;
+  for (Index start = lo; start < hi; start += 256) {
+    const Index i = start + t;
+    const bool v = i < hi && valid(i);
+    const unsigned long long mask = __ballot(v);
+    if (lane == 0) wcnt[wave] = __popcll(mask);
+    __syncthreads();
+    int woff = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      woff += w < wave ? wcnt[w] : 0;
+      tot += wcnt[w];
+    }
+    if (v) emit(base + woff + __popcll(mask & ((1ull << lane) - 1ull)), i);
+    base += tot;
+    __syncthreads();
+  }
+  return base;
+}
+
 // The per-split lists the search left in the workspace: entry (split * Nq + row) * k + rank, sorted by rank; a list that is not
 // full (fewer than k gallery rows in the split) ends in index -1.
 struct CosLists {

@@ -8,7 +8,9 @@
 // k order of the dot product) and the merge of the per-split lists by the same order gives the same list for any split count.
 //
 // Kernels:
-//   inv_norm_kernel      one wave per row: 1/|x| (0 for a zero row) of the query and gallery rows, into the workspace.
+//   inv_norm_kernel      one wave per row: 1/|x| of the query and gallery rows, into the workspace; 0 for a row that is not valid (sum
+//                        of squares finite and > 0) -- the flag rsp_repr_stats, rsp_kmeans_fit and rsp_tsne_affinities select by
+//                        (rsp_inv_norms).
 //   cos_topk_kernel<S, K1>   block = 64 queries x one gallery split.  Per gallery tile of 128 rows the 4 waves (2 x 2, 32 x 64 each)
 //                        accumulate the dot products on v_mfma_f32_32x32x2_f32 from LDS chunks of 32 k (register prefetch of the
 //                        next chunk, double-buffered LDS), scale them to similarities into an LDS score tile (aliasing the chunk
@@ -38,7 +40,7 @@ __global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= n || (stop && *stop)) return;
   const float s = rsp_row_sumsq(x + (long long)row * ld, D, lane);
-  if (lane == 0) inv[row] = s > 0.f ? 1.f / sqrtf(s) : 0.f;
+  if (lane == 0) inv[row] = (s > 0.f && s < INFINITY) ? 1.f / sqrtf(s) : 0.f;      // (a NaN fails both comparisons)
 }
 
 template <int S, bool K1>
@@ -263,6 +265,11 @@ int rsp_cos_search_check(const char* who, const float* q, int ldq, int Nq, const
   return RSP_OK;
 }
 
+int rsp_inv_norms(const float* x, int ld, int n, int D, float* inv, const int* stop, hipStream_t s) {
+  hipLaunchKernelGGL(inv_norm_kernel, dim3(rsp_cdiv(n, 4)), dim3(256), 0, s, x, ld, n, D, inv, stop);
+  return rsp_check_launch("inv_norm_kernel");
+}
+
 int rsp_cos_search(const char* who, const float* q, int ldq, int Nq, const float* g, int ldg, int Ng, int D, int k, int splits,
                    void* workspace, size_t workspace_bytes, hipStream_t s, CosLists* lists) {
   return rsp_cos_search_gated(who, q, ldq, Nq, g, ldg, Ng, D, k, splits, workspace, workspace_bytes, s, lists, nullptr, true);
@@ -280,14 +287,9 @@ int rsp_cos_search_gated(const char* who, const float* q, int ldq, int Nq, const
   lists->splits = splits;
   lists->inv_q = invq;
   lists->inv_g = invg;
-  int rc = RSP_OK;
-  if (norm_q) {
-    hipLaunchKernelGGL(inv_norm_kernel, dim3(rsp_cdiv(Nq, 4)), dim3(256), 0, s, q, ldq, Nq, D, invq, stop);
-    rc = rsp_check_launch("inv_norm_kernel");
-    if (rc != RSP_OK) return rc;
-  }
-  hipLaunchKernelGGL(inv_norm_kernel, dim3(rsp_cdiv(Ng, 4)), dim3(256), 0, s, g, ldg, Ng, D, invg, stop);
-  rc = rsp_check_launch("inv_norm_kernel");
+  int rc = norm_q ? rsp_inv_norms(q, ldq, Nq, D, invq, stop, s) : RSP_OK;
+  if (rc != RSP_OK) return rc;
+  rc = rsp_inv_norms(g, ldg, Ng, D, invg, stop, s);
   if (rc != RSP_OK) return rc;
   if (k == 1) return launch_search<1, true>(q, ldq, Nq, g, ldg, Ng, D, k, splits, invq, invg, lists->val, lists->idx, stop, s);
   switch (rsp_cdiv(k, 64)) {

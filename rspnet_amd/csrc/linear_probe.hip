@@ -7,7 +7,7 @@
 //                            f = scale / sqrtf(ss) (normalize) or scale, and the flag every later kernel selects by: ss valid and
 //                            the label inside [0, C).
 //   probe_compact_kernel    per chunk of `batch` rows: its valid rows in ascending order as a list of row indices, and their number m
-//                            (integers; ballot and prefix counts).  Every later kernel of a step walks that list, so an invalid row
+//                            (integers; rsp_compact_rows, cos_search.h).  Every later kernel of a step walks that list, so an invalid row
 //                            is not read again and the fit is, to the bit, the fit on x without it; also the counts of all of x.
 //   probe_fwd_kernel<CT, F>  cos_topk_kernel's / repr_pair_kernel's GEMM tile (64 rows, 32-wide k chunks through double-buffered
 //                            LDS, register prefetch, v_mfma_f32_32x32x2_f32, the same accumulator mapping) with the rows of x f as
@@ -76,30 +76,15 @@ __host__ __device__ __forceinline__ int probe_splits(int cap, int rows) {
 }
 
 // block c < nchunks: the valid rows of chunk c (rows [c batch, c batch + batch) of x) in ascending order into idx[c batch ..], their
-// number into mcnt[c] (ballot + prefix counts: integers, order fixed); block nchunks: the valid rows of all of x, into counts.
+// number into mcnt[c] (rsp_compact_rows: integers, order fixed); block nchunks: the valid rows of all of x, into counts.
 __global__ __launch_bounds__(256) void probe_compact_kernel(const int* __restrict__ ok, int N, int batch, int nchunks,
                                                             int* __restrict__ idx, int* __restrict__ mcnt, int* __restrict__ counts) {
-  __shared__ int wcnt[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, c = blockIdx.x;
+  const int t = threadIdx.x, c = blockIdx.x;
   const long long lo = c < nchunks ? (long long)c * batch : 0;
   const long long hi = c < nchunks ? (lo + batch < N ? lo + batch : N) : N;
-  int base = 0;
-  for (long long start = lo; start < hi; start += 256) {
-    const long long i = start + t;
-    const bool v = i < hi && ok[i] != 0;
-    const unsigned long long mask = __ballot(v);
-    if (lane == 0) wcnt[wave] = __popcll(mask);
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      woff += w < wave ? wcnt[w] : 0;
-      tot += wcnt[w];
-    }
-    if (v && c < nchunks) idx[lo + base + woff + __popcll(mask & ((1ull << lane) - 1ull))] = (int)i;
-    base += tot;
-    __syncthreads();
-  }
+  const int base = rsp_compact_rows(lo, hi, [&](long long i) { return ok[i] != 0; }, [&](int r, long long i) {
+    if (c < nchunks) idx[lo + r] = (int)i;
+  });
   if (t == 0) {
     if (c < nchunks) {
       mcnt[c] = base;
@@ -459,20 +444,6 @@ int launch_rows(const float* x, int ld, int N, int D, const long long* y, int C,
                 hipStream_t s) {
   hipLaunchKernelGGL(probe_rows_kernel, dim3(rsp_cdiv(N, 4)), dim3(256), 0, s, x, ld, N, D, y, C, normalize, scale, fac, ok);
   return rsp_check_launch("probe_rows_kernel");
-}
-
-// Launch (256 threads) of a kernel whose dynamic LDS can exceed the default limit: the attribute is raised on the instance's first
-// launch, so a capture comes after one eager call.  (repr_stats.hip's helper: common.h's rsp_launch_lds also records the kernel's name
-// for rsp_last_conv_kernel, which belongs to the convolution launchers.)
-template <auto KERNEL, class... Args>
-int launch_lds(const char* name, dim3 grid, size_t lds, hipStream_t s, Args... args) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds, s, args...);
-  return rsp_check_launch(name);
 }
 
 template <int CT, bool FUSED>

@@ -3,8 +3,8 @@
 // stored, nothing atomic.  include/rspnet_hip.h states the rule; rspnet_amd/repr_stats.py restates it in numpy fp64.
 //
 // Kernels:
-//   repr_norm_kernel     one wave per row: the fp32 sum of squares as inv_norm_kernel (cos_search.hip) forms it; inv = 1/sqrtf(ss) for a
-//                        valid row (ss finite and > 0), 0 for an invalid one -- the flag every later kernel selects by.
+//   inv_norm_kernel      the search's (rsp_inv_norms, cos_search.h): inv = 1/sqrtf(ss) for a valid row (ss finite and > 0), 0 for an
+//                        invalid one -- the flag every later kernel selects by.
 //   repr_pair_kernel     cos_topk_kernel's GEMM tile (64 x 128 rows, 32-wide k chunks through double-buffered LDS, register prefetch,
 //                        v_mfma_f32_32x32x2_f32, the same accumulator mapping) with both operands from x.  The tiles that hold some
 //                        i < j are numbered column tile by column tile: column tile tj (rows 128 tj ..) meets row tiles 0 .. 2 tj + 1, so
@@ -21,7 +21,7 @@
 //   repr_reduce_kernel   gram / colsum: the splits in split order in fp64, every element written; an element of a skipped tile is
 //                        read from its mirror image, so the matrix is symmetric to the bit.
 //   repr_final_kernel    one block: the pair partials in a fixed order in fp64, the valid / invalid row counts (integers).
-#include "common.h"
+#include "cos_search.h"
 
 #include <math.h>
 
@@ -43,20 +43,6 @@ constexpr int GR_BUF = GR_KC * GR_LD;
 constexpr size_t GR_LDS_BYTES = (size_t)2 * GR_BUF * sizeof(float);      // 49 152: three workgroups per CU
 constexpr int GR_TARGET_BLOCKS = 1024;
 constexpr int FIN_THREADS = 1024;
-
-__global__ __launch_bounds__(256) void repr_norm_kernel(const float* __restrict__ x, int ld, int n, int D, float* __restrict__ inv) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= n) return;
-  const float* p = x + (long long)row * ld;
-  float s = 0.f;
-  for (int c = 2 * lane; c < D; c += 128) {
-    const float2 v = *reinterpret_cast<const float2*>(p + c);
-    s = fmaf(v.x, v.x, s);
-    s = fmaf(v.y, v.y, s);
-  }
-  s = rsp_wave_sum(s);
-  if (lane == 0) inv[row] = (s > 0.f && s < INFINITY) ? 1.f / sqrtf(s) : 0.f;      // (a NaN fails both comparisons)
-}
 
 __global__ __launch_bounds__(256) void repr_pair_kernel(const float* __restrict__ x, int ld, int N, int D, float c,
                                                         const float* __restrict__ inv, int ntiles, int per, int nct,
@@ -374,19 +360,6 @@ int fail(const char* what, int code) {
 
 bool aligned8(const void* p) { return (((uintptr_t)p) & 7) == 0; }
 
-// Launch (256 threads) of a kernel whose dynamic LDS can exceed the default limit: the attribute is raised on the first launch, so a
-// capture comes after one eager call.
-template <auto KERNEL, class... Args>
-int launch_lds(const char* name, dim3 grid, size_t lds, hipStream_t s, Args... args) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds, s, args...);
-  return rsp_check_launch(name);
-}
-
 }  // namespace
 
 size_t rsp_repr_stats_workspace(int32_t N, int32_t D) { return sizes_ok(N, D) ? make_plan(N, D).bytes : 0; }
@@ -409,8 +382,7 @@ int rsp_repr_stats(const float* x, int32_t ld, int32_t N, int32_t D, float c, rs
   float* gpart = reinterpret_cast<float*>(ws + p.off_gpart);
   float* cpart = reinterpret_cast<float*>(ws + p.off_cpart);
 
-  hipLaunchKernelGGL(repr_norm_kernel, dim3(rsp_cdiv(N, 4)), dim3(256), 0, s, x, ld, N, D, inv);
-  int rc = rsp_check_launch("repr_norm_kernel");
+  int rc = rsp_inv_norms(x, ld, N, D, inv, nullptr, s);
   if (rc != RSP_OK) return rc;
   rc = launch_lds<repr_pair_kernel>("repr_pair_kernel", dim3(p.blocks), RP_LDS_BYTES, s, x, (int)ld, (int)N, (int)D, c, (const float*)inv,
                                     p.ntiles, p.per, p.nct, part);

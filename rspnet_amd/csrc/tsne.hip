@@ -3,9 +3,8 @@
 // include/rspnet_hip.h states the rule; rspnet_amd/tsne.py restates it in numpy fp64 (tsne_reference).
 //
 // Kernels of the affinities:
-//   ts_norm_kernel      one wave per row: inv = 1 / sqrtf(ss) with ss from rsp_row_sumsq (the search's routine) for a valid row
-//                       (ss finite and > 0), 0 otherwise.
-//   ts_compact_kernel   one block: the valid rows in ascending order as a list (km_compact_kernel's ballot + prefix counts), -1 behind
+//   inv_norm_kernel     the search's (rsp_inv_norms, cos_search.h): inv = 1 / sqrtf(ss) for a valid row (ss finite and > 0), 0 otherwise.
+//   ts_compact_kernel   one block: the valid rows in ascending order as a list (rsp_compact_rows, cos_search.h), -1 behind
 //                       it; invc[rank] = the inverse norm of the listed row; M, rows_valid and rows_bad.  Every later kernel walks the
 //                       list by rank, so the result is, to the bit, the result on x without the invalid rows.
 //   ts_dist_kernel      repr_pair_kernel's GEMM tile (64 x 128 ranks, 32-wide k chunks through double-buffered LDS, register prefetch,
@@ -56,40 +55,14 @@ __host__ __device__ __forceinline__ int ts_splits(int m) {
   return s < 1 ? 1 : s;
 }
 
-__global__ __launch_bounds__(256) void ts_norm_kernel(const float* __restrict__ x, int ld, int n, int D, float* __restrict__ inv) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= n) return;
-  const float s = rsp_row_sumsq(x + (long long)row * ld, D, lane);
-  if (lane == 0) inv[row] = (s > 0.f && s < INFINITY) ? 1.f / sqrtf(s) : 0.f;      // (a NaN fails both comparisons)
-}
-
 __global__ __launch_bounds__(256) void ts_compact_kernel(const float* __restrict__ inv, int N, int* __restrict__ rows,
                                                          float* __restrict__ invc, TsState* __restrict__ st,
                                                          rsp_tsne_info* __restrict__ info) {
-  __shared__ int wcnt[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int base = 0;
-  for (int start = 0; start < N; start += 256) {
-    const int i = start + t;
-    const float iv = i < N ? inv[i] : 0.f;
-    const bool v = iv > 0.f;
-    const unsigned long long mask = __ballot(v);
-    if (lane == 0) wcnt[wave] = __popcll(mask);
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      woff += w < wave ? wcnt[w] : 0;
-      tot += wcnt[w];
-    }
-    if (v) {
-      const int r = base + woff + __popcll(mask & ((1ull << lane) - 1ull));
-      rows[r] = i;
-      invc[r] = iv;
-    }
-    base += tot;
-    __syncthreads();
-  }
+  const int t = threadIdx.x;
+  const int base = rsp_compact_rows(0, N, [&](int i) { return inv[i] > 0.f; }, [&](int r, int i) {
+    rows[r] = i;
+    invc[r] = inv[i];
+  });
   for (int r = base + t; r < N; r += 256) rows[r] = -1;
   if (t == 0) {
     st->m = base;
@@ -551,8 +524,7 @@ int rsp_tsne_affinities(const float* x, int32_t ld, int32_t N, int32_t D, float 
   float* d = dmat ? dmat : reinterpret_cast<float*>(ws + p.off_dmat);
   const int ldd = dmat ? ldp : N;      // (dmat, when given, has pmat's pitch)
 
-  hipLaunchKernelGGL(ts_norm_kernel, dim3(rsp_cdiv(N, 4)), dim3(256), 0, s, x, (int)ld, (int)N, (int)D, inv);
-  int rc = rsp_check_launch("ts_norm_kernel");
+  int rc = rsp_inv_norms(x, ld, N, D, inv, nullptr, s);
   if (rc != RSP_OK) return rc;
   hipLaunchKernelGGL(ts_compact_kernel, dim3(1), dim3(256), 0, s, (const float*)inv, (int)N, (int*)rows, invc, st, info);
   rc = rsp_check_launch("ts_compact_kernel");

@@ -26,6 +26,7 @@ classifies the test features ``rspnet_amd.retrieval`` saved against its train fe
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import logging
 import math
@@ -39,6 +40,7 @@ from torch import Tensor, nn
 
 from . import finetune as _ft
 from . import ops as _ops
+from .framework.monitor import EpochMonitor
 
 logger = logging.getLogger(__name__)
 MAX_K, MAX_CLASSES, MIN_T = 256, 1024, 0.01
@@ -158,13 +160,11 @@ def synthetic_loaders(bank_samples: int, query_samples: int, batch_size: int, nu
     return bank, query
 
 
-def extract_bank_and_query(model: nn.Module, encoder: str, bank_loader: Iterable, query_loader: Iterable, n_crop: int = 1):
-    """(g, y_g, q, y_q, valid): ``extract`` of both loaders through encoder 'q' or 'k' of the pretext model (or its wrapper with
-    ``.module``) in eval mode, every module's ``training`` flag put back afterwards; valid: the query loader's count of real samples.
-    What the kNN monitor and the linear-probe monitor share."""
+@contextlib.contextmanager
+def frozen_encoder(model: nn.Module, encoder: str):
+    """Encoder 'q' or 'k' of the pretext model (or its wrapper with ``.module``) with the whole model in eval mode; every module's
+    ``training`` flag is put back on the way out.  What every monitor that extracts features goes through."""
     net = getattr(model, "module", model)
-    enc = net.encoder_q if encoder == "q" else net.encoder_k
-    device = next(enc.parameters()).device
     flags = [(m, m.training) for m in net.modules()]
     try:
         net.eval()
@@ -172,62 +172,78 @@ def extract_bank_and_query(model: nn.Module, encoder: str, bank_loader: Iterable
             if not net._q_params:
                 net._q_params = list(net.encoder_q.parameters())
             net._check_q_weights()
-        # a bank of split 'train' has n_crop = 1 clips; only the query side carries crops
-        n_crop_bank = 1 if getattr(bank_loader, "split", None) == "train" else n_crop
-        g, y_g = extract(enc, bank_loader, device, n_crop_bank)
-        q, y_q = extract(enc, query_loader, device, n_crop)
+        yield net.encoder_q if encoder == "q" else net.encoder_k
     finally:
         for m, was in flags:
             m.training = was
+
+
+def extract_bank(enc: nn.Module, bank_loader: Iterable, n_crop: int = 1):
+    """``extract`` of a bank through the encoder ``frozen_encoder`` yields; a bank of split 'train' has n_crop = 1 clips."""
+    n_crop_bank = 1 if getattr(bank_loader, "split", None) == "train" else n_crop
+    return extract(enc, bank_loader, next(enc.parameters()).device, n_crop_bank)
+
+
+def extract_bank_and_query(model: nn.Module, encoder: str, bank_loader: Iterable, query_loader: Iterable, n_crop: int = 1):
+    """(g, y_g, q, y_q, valid): ``extract`` of both loaders through encoder 'q' or 'k' of the pretext model in eval mode
+    (``frozen_encoder``); only the query side carries crops; valid: the query loader's count of real samples.  What the kNN monitor
+    and the linear-probe monitor share."""
+    with frozen_encoder(model, encoder) as enc:
+        g, y_g = extract_bank(enc, bank_loader, n_crop)
+        q, y_q = extract(enc, query_loader, next(enc.parameters()).device, n_crop)
     valid = query_loader.num_valid_samples() if hasattr(query_loader, "num_valid_samples") else q.shape[0]
     return g, y_g, q, y_q, min(int(valid), q.shape[0])
 
 
-class KNNMonitor:
+# ---- valid rows, as the cluster and t-SNE modules decide them ------------------------------------------------------------------
+def _valid_rows_np(x32: np.ndarray) -> np.ndarray:
+    """The fp32 sum of squares of the row is finite and > 0."""
+    with np.errstate(all="ignore"):
+        ss = (x32 * x32).sum(axis=1, dtype=np.float32)
+        return np.isfinite(ss) & (ss > 0)
+
+
+def _valid_rows_torch(x: Tensor) -> Tensor:
+    ss = (x * x).sum(dim=1)
+    return torch.isfinite(ss) & (ss > 0)
+
+
+def _rows(x: Tensor) -> Tensor:
+    """x as the fp32 matrix the row kernels take: unit column stride, an even row pitch."""
+    x = x.to(torch.float32)
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) % 2):
+        x = x.contiguous()
+    return x
+
+
+class KNNMonitor(EpochMonitor):
     """Every ``every``-th epoch (and on the last one): weighted kNN accuracy of a labelled query set against a labelled bank on the
     features of one encoder of the pretext model.  ``run`` leaves the model as it found it -- state_dict() bit for bit (eval-mode
     BatchNorm moves no statistics, no queue or counter is touched), every module's ``training`` flag -- draws from no global random
-    generator and refuses to run inside a graph capture."""
+    generator and refuses to run inside a graph capture.  Config, e.g. {"every": 1, "k": 200, "t": 0.07, "num_classes": 101,
+    "encoder": "q", "bank_samples": 256, "query_samples": 128, "batch_size": 32, "n_crop": 1}."""
+
+    KEY = "knn_monitor"
+    KEYS = ("every", "k", "t", "num_classes", "encoder", "bank_samples", "query_samples", "batch_size", "n_crop")
 
     def __init__(self, every: int, num_epochs: int, k: int = 200, t: float = 0.07, num_classes: int = 101, encoder: str = "q",
                  bank_samples: int = 256, query_samples: int = 128, batch_size: int = 32, n_crop: int = 1):
         check_limits(k, t, num_classes)
-        if encoder not in ("q", "k"):
-            raise ValueError(f"knn_monitor: encoder must be 'q' or 'k', got {encoder!r}")
-        if int(every) < 1 or min(int(bank_samples), int(query_samples), int(batch_size), int(n_crop)) < 1:
-            raise ValueError("knn_monitor: every, bank_samples, query_samples, batch_size and n_crop must be at least 1")
+        self._check_encoder(encoder)
+        self._check_at_least_1(every=every, bank_samples=bank_samples, query_samples=query_samples, batch_size=batch_size, n_crop=n_crop)
         self.every, self.num_epochs = int(every), int(num_epochs)
         self.k, self.t, self.num_classes, self.encoder = int(k), float(t), int(num_classes), encoder
         self.bank_samples, self.query_samples = int(bank_samples), int(query_samples)
         self.batch_size, self.n_crop = int(batch_size), int(n_crop)
 
-    @classmethod
-    def from_config(cls, cfg, num_epochs: int) -> Optional["KNNMonitor"]:
-        """The ``knn_monitor`` key of a pretext config, e.g. {"every": 1, "k": 200, "t": 0.07, "num_classes": 101, "encoder": "q",
-        "bank_samples": 256, "query_samples": 128, "batch_size": 32, "n_crop": 1}; None -- nothing constructed, no launch ever
-        added -- when the key is absent or ``every`` is 0."""
-        node = cfg.get("knn_monitor") if hasattr(cfg, "get") else None
-        if not node or int(node.get("every", 0)) <= 0:
-            return None
-        known = ("every", "k", "t", "num_classes", "encoder", "bank_samples", "query_samples", "batch_size", "n_crop")
-        extra = sorted(set(node) - set(known))
-        if extra:
-            raise ValueError(f"knn_monitor: unknown keys {extra}")
-        return cls(num_epochs=num_epochs, **{key: node[key] for key in known if key in node})
-
-    def due(self, epoch: int) -> bool:
-        """``epoch``: the 0-based epoch that has just finished its last step."""
-        return (int(epoch) + 1) % self.every == 0 or int(epoch) + 1 == self.num_epochs
-
-    def build_loaders(self, T: int, size: int, device, seed: int = 0):
+    def build_loaders(self, T: int, size: int, device, seed: int = 0) -> tuple:
         """The stand-in data: two ``SyntheticLabelledClips``, bank = split 'train' (order fixed by its epoch 0), query = split 'val'."""
         return synthetic_loaders(self.bank_samples, self.query_samples, self.batch_size, self.num_classes, self.n_crop, T, size, device, seed)
 
     def run(self, model: nn.Module, bank_loader: Iterable, query_loader: Iterable, return_features: bool = False) -> dict:
         """{"acc1", "acc5", "n_bank", "n_query", "seconds"}, with ``return_features`` also "bank_features": the (n_bank, D) backbone
         features it extracted, on the device.  ``model``: the pretext model (or its wrapper with ``.module``)."""
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("KNNMonitor.run: never inside a graph capture")
+        self._refuse_capture()
         t0 = time.perf_counter()
         g, y_g, q, y_q, valid = extract_bank_and_query(model, self.encoder, bank_loader, query_loader, self.n_crop)
         res = knn_classify(q, y_q, g, y_g, self.k, self.t, self.num_classes, valid=valid)
@@ -236,6 +252,20 @@ class KNNMonitor:
         if return_features:
             out["bank_features"] = g
         return out
+
+    def run_epoch(self, model, loaders: tuple, ctx: dict) -> dict:
+        """With the representation monitor due as well, the bank's backbone features are left in ctx for it."""
+        r = self.run(model, *loaders, **({"return_features": True} if "repr_monitor" in ctx["due"] else {}))
+        ctx["bank_features"] = r.pop("bank_features", None)
+        return r
+
+    def scalars(self, result: dict) -> dict:
+        return {"knn/acc1": result["acc1"], "knn/acc5": result["acc5"]}
+
+    def log_line(self, result: dict, ctx: dict) -> str:
+        r = result
+        return (f"kNN [{ctx['epoch']}/{ctx['num_epochs']}]\tAcc@1 {r['acc1']:.2f}\tAcc@5 {r['acc5']:.2f}"
+                f"\t(k={self.k}, T={self.t}, bank {r['n_bank']}, query {r['n_query']}, {r['seconds']:.1f} s)")
 
 
 # ---- command line over saved retrieval features --------------------------------------------------------------------------

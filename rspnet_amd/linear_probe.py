@@ -43,6 +43,7 @@ from torch import Tensor, nn
 from . import finetune as _ft
 from . import knn as _knn
 from . import ops as _ops
+from .framework.monitor import EpochMonitor
 
 logger = logging.getLogger(__name__)
 MAX_CLASSES, MAX_D = 1024, 4096
@@ -289,20 +290,23 @@ def evaluate(probe: Probe, x: Tensor, y: Tensor, valid: Optional[int] = None) ->
 
 
 # ---- the pretext driver's hook -------------------------------------------------------------------------------------------
-class LinearProbeMonitor:
+class LinearProbeMonitor(EpochMonitor):
     """Every ``every``-th epoch (and on the last one): a probe fitted on the backbone features of a labelled bank and evaluated on
     those of a labelled query set, both from one encoder of the pretext model (``knn.extract``).  ``run`` leaves the model as it
     found it -- state_dict() bit for bit, every module's ``training`` flag --, draws from no global random generator and refuses to
     run inside a graph capture.  The extraction and the stand-in loaders are the kNN monitor's (``knn.extract_bank_and_query``,
-    ``knn.synthetic_loaders``); each monitor still extracts for itself, since ``KNNMonitor.run`` hands back the bank's features only."""
+    ``knn.synthetic_loaders``); each monitor still extracts for itself, since ``KNNMonitor.run`` hands back the bank's features only.
+    Config, e.g. {"every": 10, "num_classes": 101, "steps": 100, "lr": 0.125}."""
+
+    KEY = "probe_monitor"
+    KEYS = ("every", "num_classes", "encoder", "bank_samples", "query_samples", "batch_size", "n_crop", "steps", "lr", "momentum",
+            "weight_decay", "scale", "batch")
 
     def __init__(self, every: int, num_epochs: int, num_classes: int = 101, encoder: str = "q", bank_samples: int = 256,
                  query_samples: int = 128, batch_size: int = 32, n_crop: int = 1, steps: int = 100, lr: float = 0.125,
                  momentum: float = 0.9, weight_decay: float = 1e-4, scale: float = 8.0, batch: Optional[int] = None):
-        if encoder not in ("q", "k"):
-            raise ValueError(f"probe_monitor: encoder must be 'q' or 'k', got {encoder!r}")
-        if int(every) < 1 or min(int(bank_samples), int(query_samples), int(batch_size), int(n_crop)) < 1:
-            raise ValueError("probe_monitor: every, bank_samples, query_samples, batch_size and n_crop must be at least 1")
+        self._check_encoder(encoder)
+        self._check_at_least_1(every=every, bank_samples=bank_samples, query_samples=query_samples, batch_size=batch_size, n_crop=n_crop)
         check_limits(bank_samples, 2, num_classes, bank_samples if batch is None else batch, steps)
         self.every, self.num_epochs = int(every), int(num_epochs)
         self.num_classes, self.encoder = int(num_classes), encoder
@@ -311,34 +315,14 @@ class LinearProbeMonitor:
         self.steps, self.lr, self.momentum, self.weight_decay = int(steps), float(lr), float(momentum), float(weight_decay)
         self.scale, self.batch = float(scale), None if batch is None else int(batch)
 
-    KEYS = ("every", "num_classes", "encoder", "bank_samples", "query_samples", "batch_size", "n_crop", "steps", "lr", "momentum",
-            "weight_decay", "scale", "batch")
-
-    @classmethod
-    def from_config(cls, cfg, num_epochs: int) -> Optional["LinearProbeMonitor"]:
-        """The ``probe_monitor`` key of a pretext config, e.g. {"every": 10, "num_classes": 101, "steps": 100, "lr": 0.125}; None --
-        nothing constructed, no launch ever added -- when the key is absent or ``every`` is 0."""
-        node = cfg.get("probe_monitor") if hasattr(cfg, "get") else None
-        if not node or int(node.get("every", 0)) <= 0:
-            return None
-        extra = sorted(set(node) - set(cls.KEYS))
-        if extra:
-            raise ValueError(f"probe_monitor: unknown keys {extra}")
-        return cls(num_epochs=num_epochs, **{key: node[key] for key in cls.KEYS if key in node})
-
-    def due(self, epoch: int) -> bool:
-        """``epoch``: the 0-based epoch that has just finished its last step."""
-        return (int(epoch) + 1) % self.every == 0 or int(epoch) + 1 == self.num_epochs
-
-    def build_loaders(self, T: int, size: int, device, seed: int = 0):
+    def build_loaders(self, T: int, size: int, device, seed: int = 0) -> tuple:
         """The stand-in data of the kNN monitor: bank = split 'train', query = split 'val' of ``SyntheticLabelledClips``."""
         return _knn.synthetic_loaders(self.bank_samples, self.query_samples, self.batch_size, self.num_classes, self.n_crop, T, size, device,
                                       seed)
 
     def run(self, model: nn.Module, bank_loader: Iterable, query_loader: Iterable) -> dict:
         """{"acc1", "acc5", "loss", "train_loss", "n_bank", "n_query", "bad_rows", "seconds"}."""
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("LinearProbeMonitor.run: never inside a graph capture")
+        self._refuse_capture()
         t0 = time.perf_counter()
         g, y_g, q, y_q, valid = _knn.extract_bank_and_query(model, self.encoder, bank_loader, query_loader, self.n_crop)
         with torch.no_grad():
@@ -348,6 +332,15 @@ class LinearProbeMonitor:
             res = evaluate(probe, q, y_q, valid=valid)
         return {"acc1": res["acc1"], "acc5": res["acc5"], "loss": res["loss"], "train_loss": float(probe.loss_trace[-1]),
                 "n_bank": int(g.shape[0]), "n_query": res["n"], "bad_rows": int(probe.counts[1]), "seconds": time.perf_counter() - t0}
+
+    def scalars(self, result: dict) -> dict:
+        return {f"probe_{k}": result[k] for k in ("acc1", "acc5", "loss")}
+
+    def log_line(self, result: dict, ctx: dict) -> str:
+        r = result
+        return (f"Probe [{ctx['epoch']}/{ctx['num_epochs']}]\tAcc@1 {r['acc1']:.2f}\tAcc@5 {r['acc5']:.2f}\tloss {r['loss']:.4f}"
+                f"\t({self.steps} steps, lr {self.lr}, bank {r['n_bank']}, query {r['n_query']}, {r['bad_rows']} bad, "
+                f"{r['seconds']:.1f} s)")
 
 
 # ---- command line over saved retrieval features --------------------------------------------------------------------------

@@ -22,18 +22,27 @@ from pathlib import Path
 
 import torch
 
-from . import _lib, cluster, fingerprint, knn, linear_probe, ops, repr_stats, tsne
+from . import _lib, fingerprint, ops
+from .cluster import ClusterMonitor
 from .framework.arguments import RUN_DIR_NAME_REGEX, add_driver_arguments, parse_driver_args, save_run_files  # noqa: F401
 from .framework.driver import (append_scalars, finish_process_group, init_process_group, launch, load_config, load_states, save_run,
                                seed_everything, setup_logging, visible_gpu_count)
 from .framework.meters import DeviceMeters
 from .framework.utils.checkpoint import CheckpointManager
 from .framework.utils.environment import scale_learning_rate
+from .knn import KNNMonitor
+from .linear_probe import LinearProbeMonitor
 from .moco import Loss, ModelFactory
 from .optim import SGD
+from .repr_stats import ReprMonitor
+from .tsne import TsneMonitor
 from .utils.moco import replace_moco_k_in_config
 
 logger = logging.getLogger(__name__)
+
+# The opt-in epoch-end monitors (framework/monitor.py), in the order they run and their scalars are written.  Each is its config key
+# (the class's KEY) away, e.g. -x '{KEY: {"every": 10}}'; a new one is a subclass of EpochMonitor appended here.
+MONITORS = (KNNMonitor, ReprMonitor, LinearProbeMonitor, ClusterMonitor, TsneMonitor)
 
 
 def accuracy(output: torch.Tensor, target: torch.Tensor, topk=(1,)):
@@ -175,37 +184,15 @@ class Engine:
                                                seed=args.seed + local_rank, aug_plus=bool(cfg.get("moco", {}).get("aug_plus", False)))
         self.train_loader = train_loader or SyntheticClips(self.batch_size, T, size, args.steps_per_epoch, self.device,
                                                            seed=args.seed + local_rank)
-        # opt-in (config key "knn_monitor", e.g. -x '{"knn_monitor": {"every": 10, "num_classes": 101}}'): None otherwise.  Rank 0
-        # classifies; knn_loaders: a (bank, query) pair yielding ((clip,), target), the synthetic labelled clips by default
-        self.knn = knn.KNNMonitor.from_config(cfg, self.num_epochs)
-        self.knn_loaders, self._knn_result = knn_loaders, None
-        if self.knn is not None and knn_loaders is None and local_rank == 0:
-            self.knn_loaders = self.knn.build_loaders(T, size, self.device, seed=args.seed)
-        # opt-in (config key "repr_monitor", e.g. -x '{"repr_monitor": {"every": 10, "t": 2.0}}'): None otherwise.  Rank 0 reads the
-        # queue (rank-identical by construction); no labels, no loaders
-        self.repr_monitor = repr_stats.ReprMonitor.from_config(cfg, self.num_epochs)
-        self._repr_result, self._bank_features = None, None
-        # opt-in (config key "probe_monitor", e.g. -x '{"probe_monitor": {"every": 10, "num_classes": 101, "steps": 100}}'): None
-        # otherwise.  Rank 0 fits a linear probe on the bank's features and evaluates it on the query's; the loaders are its own
-        # (the kNN monitor's keys and stand-in data), so the two monitors extract separately
-        self.probe = linear_probe.LinearProbeMonitor.from_config(cfg, self.num_epochs)
-        self.probe_loaders, self._probe_result = None, None
-        if self.probe is not None and local_rank == 0:
-            self.probe_loaders = self.probe.build_loaders(T, size, self.device, seed=args.seed)
-        # opt-in (config key "cluster_monitor", e.g. -x '{"cluster_monitor": {"every": 10, "num_clusters": 101, "num_classes": 101}}'):
-        # None otherwise.  Rank 0 clusters the bank's features (the kNN monitor's stand-in bank loader, its own instance) and scores
-        # the clusters against the labels
-        self.cluster = cluster.ClusterMonitor.from_config(cfg, self.num_epochs)
-        self.cluster_loader, self._cluster_result = None, None
-        if self.cluster is not None and local_rank == 0:
-            self.cluster_loader = self.cluster.build_loader(T, size, self.device, seed=args.seed)
-        # opt-in (config key "tsne_monitor", e.g. -x '{"tsne_monitor": {"every": 10, "perplexity": 30, "iters": 500}}'): None
-        # otherwise.  Rank 0 maps the bank's features (the kNN monitor's stand-in bank loader, its own instance) with t-SNE and
-        # writes tsne_epoch{E}.png / .npy into the run directory
-        self.tsne = tsne.TsneMonitor.from_config(cfg, self.num_epochs)
-        self.tsne_loader, self._tsne_result = None, None
-        if self.tsne is not None and local_rank == 0:
-            self.tsne_loader = self.tsne.build_loader(T, size, self.device, seed=args.seed)
+        # MONITORS: built on every rank (None for a key the config does not carry); rank 0 runs them on loaders of its own -- the
+        # stand-in labelled clips of each monitor, or knn_loaders: a (bank, query) pair yielding ((clip,), target) for the kNN monitor
+        self.monitors = [m for m in (cls.from_config(cfg, self.num_epochs) for cls in MONITORS) if m is not None]
+        self.monitor_loaders, self.monitor_results = {}, {}
+        for m in self.monitors:
+            if knn_loaders is not None and isinstance(m, KNNMonitor):
+                self.monitor_loaders[m.KEY] = tuple(knn_loaders)
+            elif local_rank == 0:
+                self.monitor_loaders[m.KEY] = m.build_loaders(T, size, self.device, seed=args.seed)
 
     # ---- checkpoints (pretrain.py:112-132) ---------------------------------------------------------------------------
     def load_checkpoint(self, path):
@@ -290,106 +277,25 @@ class Engine:
         """One line per epoch in RUN_DIR/scalars.jsonl (rank 0): what pretrain.py:199-218,240 hands to the summary writer."""
         rec = {"epoch": self.current_epoch, "train/lr": lr}
         rec.update({f"train/{k}": self.stats[k]["avg"] for k in ("loss", "loss_A", "acc1_A", "acc5_A", "loss_M", "acc1_M")})
-        if self._knn_result is not None:
-            rec.update({"knn/acc1": self._knn_result["acc1"], "knn/acc5": self._knn_result["acc5"]})
-        if self._repr_result is not None:
-            rec.update(self._repr_result)
-        if self._probe_result is not None:
-            rec.update({f"probe_{k}": self._probe_result[k] for k in ("acc1", "acc5", "loss")})
-        cl = getattr(self, "_cluster_result", None)      # (a stand-in engine of the driver tests may not carry it)
-        if cl is not None:
-            rec.update({f"cluster_{k}": cl[k] for k in ("nmi", "ari", "purity", "objective", "iters", "empty")})
-        ts = getattr(self, "_tsne_result", None)
-        if ts is not None:
-            rec.update({"tsne_kl": ts["kl"], "tsne_purity": ts["purity"]})
+        for m in self.monitors:
+            if m.KEY in self.monitor_results:
+                rec.update(m.scalars(self.monitor_results[m.KEY]))
         append_scalars(self.scalars_path, rec)
 
-    def _run_knn_monitor(self):
-        """After the epoch's last step (train_epoch has waited for it) and before its scalar line: rank 0 classifies eagerly, in eval
-        mode, on the current stream; the other ranks wait at a barrier.  Has run on one GPU only."""
-        self._knn_result = None
-        m = self.knn
-        if m is None or not m.due(self.current_epoch):
-            return
-        if self.local_rank == 0:
-            # with the representation monitor due as well, the bank's backbone features go through it too
-            want_bank = self.repr_monitor is not None and self.repr_monitor.due(self.current_epoch)
-            r = self._knn_result = m.run(self.model, *self.knn_loaders, **({"return_features": True} if want_bank else {}))
-            self._bank_features = r.pop("bank_features", None)
-            logger.info(f"kNN [{self.current_epoch}/{self.num_epochs}]\tAcc@1 {r['acc1']:.2f}\tAcc@5 {r['acc5']:.2f}"
-                        f"\t(k={m.k}, T={m.t}, bank {r['n_bank']}, query {r['n_query']}, {r['seconds']:.1f} s)")
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            torch.distributed.barrier()
-
-    def _run_repr_monitor(self):
-        """After the kNN monitor and before the epoch's scalar line: rank 0 computes the label-free statistics of the queue -- and of
-        the bank features when the kNN monitor has just extracted them -- eagerly on the current stream; the other ranks wait at a
-        barrier.  Has run on one GPU only."""
-        self._repr_result = None
-        bank, self._bank_features = self._bank_features, None
-        m = self.repr_monitor
-        if m is None or not m.due(self.current_epoch):
-            return
-        if self.local_rank == 0:
-            r = m.run(self.model)
-            rec = {f"repr/{k}": r[k] for k in ("uniformity", "mean_cos", "effective_rank", "dim_std_min", "bad_rows")}
-            line = (f"Repr [{self.current_epoch}/{self.num_epochs}]\tuniformity {r['uniformity']:.4f}\teff.rank "
-                    f"{r['effective_rank']:.1f}/{self.model.module.queue.shape[0]}\tmean cos {r['mean_cos']:.4f}\tdim std min "
-                    f"{r['dim_std_min']:.3f}\t(t={m.t}, {r['rows']} rows, {r['bad_rows']} bad, {r['seconds']:.2f} s)")
-            if bank is not None:
-                b = repr_stats.repr_stats(bank, m.t)
-                rec.update({f"repr/bank_{k}": b[k] for k in ("uniformity", "effective_rank", "dim_std_min")})
-                line += f"\tbank: uniformity {b['uniformity']:.4f}\teff.rank {b['effective_rank']:.1f}/{bank.shape[1]}"
-            self._repr_result = rec
-            logger.info(line)
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            torch.distributed.barrier()
-
-    def _run_probe_monitor(self):
-        """After the other monitors and before the epoch's scalar line: rank 0 extracts, fits and evaluates eagerly on the current
-        stream (train_epoch has waited for the epoch's last step; nothing here is captured); the other ranks wait at a barrier.
-        Has run on one GPU only."""
-        self._probe_result = None
-        m = self.probe
-        if m is None or not m.due(self.current_epoch):
-            return
-        if self.local_rank == 0:
-            r = self._probe_result = m.run(self.model, *self.probe_loaders)
-            logger.info(f"Probe [{self.current_epoch}/{self.num_epochs}]\tAcc@1 {r['acc1']:.2f}\tAcc@5 {r['acc5']:.2f}\tloss {r['loss']:.4f}"
-                        f"\t({m.steps} steps, lr {m.lr}, bank {r['n_bank']}, query {r['n_query']}, {r['bad_rows']} bad, "
-                        f"{r['seconds']:.1f} s)")
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            torch.distributed.barrier()
-
-    def _run_cluster_monitor(self):
-        """After the other monitors and before the epoch's scalar line: rank 0 extracts, clusters and scores eagerly on the current
-        stream (nothing here is captured); the other ranks wait at a barrier.  Has run on one GPU only."""
-        self._cluster_result = None
-        m = self.cluster
-        if m is None or not m.due(self.current_epoch):
-            return
-        if self.local_rank == 0:
-            r = self._cluster_result = m.run(self.model, self.cluster_loader)
-            logger.info(f"Cluster [{self.current_epoch}/{self.num_epochs}]\tNMI {r['nmi']:.4f}\tARI {r['ari']:.4f}\tpurity {r['purity']:.4f}"
-                        f"\tobjective {r['objective']:.4f}\t({m.num_clusters} clusters, {r['iters']} iterations, {r['empty']} empty, "
-                        f"bank {r['n_bank']}, {r['bad_rows']} bad, {r['seconds']:.1f} s)")
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            torch.distributed.barrier()
-
-    def _run_tsne_monitor(self):
-        """After the other monitors and before the epoch's scalar line: rank 0 extracts and maps eagerly on the current stream (nothing
-        here is captured); the other ranks wait at a barrier.  Has run on one GPU only."""
-        self._tsne_result = None
-        m = getattr(self, "tsne", None)      # (a stand-in engine of the driver tests may not carry it)
-        if m is None or not m.due(self.current_epoch):
-            return
-        if self.local_rank == 0:
-            prefix = os.path.join(os.path.dirname(str(self.scalars_path)), f"tsne_epoch{self.current_epoch}")
-            r = self._tsne_result = m.run(self.model, self.tsne_loader, prefix)
-            logger.info(f"t-SNE [{self.current_epoch}/{self.num_epochs}]\tKL {r['kl']:.4f}\tpurity@10 {r['purity']:.4f}"
-                        f"\t(perplexity {m.perplexity:g}, {m.iters} iterations, bank {r['n_bank']}, {r['bad_rows']} bad, {r['seconds']:.1f} s)")
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            torch.distributed.barrier()
+    def _run_monitors(self):
+        """After the epoch's last step (train_epoch has waited for it) and before its scalar line, every due monitor in list order: rank 0
+        runs it eagerly on the current stream (nothing here is captured) and logs its line; the other ranks wait at a barrier, one per
+        due monitor.  The monitors have run on one GPU only."""
+        self.monitor_results = {}
+        due = [m for m in self.monitors if m.due(self.current_epoch)]
+        ctx = {"epoch": self.current_epoch, "num_epochs": self.num_epochs, "run_dir": os.path.dirname(str(self.scalars_path)),
+               "due": tuple(m.KEY for m in due)}
+        for m in due:
+            if self.local_rank == 0:
+                r = self.monitor_results[m.KEY] = m.run_epoch(self.model, self.monitor_loaders[m.KEY], ctx)
+                logger.info(m.log_line(r, ctx))
+            if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                torch.distributed.barrier()
 
     def run(self):
         num_epochs = 1 if self.args.debug else self.num_epochs
@@ -405,11 +311,7 @@ class Engine:
         while self.current_epoch < num_epochs:
             lr = float(self.optimizer.param_groups[0]["lr"])
             stats = self.train_epoch()
-            self._run_knn_monitor()
-            self._run_repr_monitor()
-            self._run_probe_monitor()
-            self._run_cluster_monitor()
-            self._run_tsne_monitor()
+            self._run_monitors()
             self.scheduler.step()
             self._write_scalars(lr)
             self.current_epoch += 1

@@ -33,14 +33,13 @@ import logging
 import math
 import os
 import time
-from typing import Optional
-
 import numpy as np
 import torch
 from torch import Tensor, nn
 
 from . import _lib
 from . import ops as _ops
+from .framework.monitor import EpochMonitor
 
 logger = logging.getLogger(__name__)
 MAX_T = 32.0
@@ -155,44 +154,53 @@ def repr_stats(x: Tensor, t: float = 2.0) -> dict:
 
 
 # ---- the pretext driver's hook -------------------------------------------------------------------------------------------
-class ReprMonitor:
+class ReprMonitor(EpochMonitor):
     """Every ``every``-th epoch (and on the last one): ``repr_stats`` of the pretext model's queue, the last K key embeddings as K x dim
     rows.  ``run`` reads the queue and nothing else: the model stays as it was bit for bit, no generator is drawn from, and it
-    refuses to run inside a graph capture."""
+    refuses to run inside a graph capture.  Config, e.g. {"every": 1, "t": 2.0}; no labels, no loaders."""
+
+    KEY = "repr_monitor"
+    KEYS = ("every", "t")
 
     def __init__(self, every: int, num_epochs: int, t: float = 2.0):
         check_limits(t)
-        if int(every) < 1:
-            raise ValueError("repr_monitor: every must be at least 1")
+        self._check_at_least_1(every=every)
         self.every, self.num_epochs, self.t = int(every), int(num_epochs), float(t)
-
-    @classmethod
-    def from_config(cls, cfg, num_epochs: int) -> Optional["ReprMonitor"]:
-        """The ``repr_monitor`` key of a pretext config, e.g. {"every": 1, "t": 2.0}; None -- nothing constructed, no launch ever
-        added -- when the key is absent or ``every`` is 0."""
-        node = cfg.get("repr_monitor") if hasattr(cfg, "get") else None
-        if not node or int(node.get("every", 0)) <= 0:
-            return None
-        known = ("every", "t")
-        extra = sorted(set(node) - set(known))
-        if extra:
-            raise ValueError(f"repr_monitor: unknown keys {extra}")
-        return cls(num_epochs=num_epochs, **{key: node[key] for key in known if key in node})
-
-    def due(self, epoch: int) -> bool:
-        """``epoch``: the 0-based epoch that has just finished its last step."""
-        return (int(epoch) + 1) % self.every == 0 or int(epoch) + 1 == self.num_epochs
 
     def run(self, model: nn.Module) -> dict:
         """``repr_stats`` of the queue plus "seconds".  ``model``: the pretext model (or its wrapper with ``.module``)."""
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("ReprMonitor.run: never inside a graph capture")
+        self._refuse_capture()
         t0 = time.perf_counter()
         net = getattr(model, "module", model)
         with torch.no_grad():
             out = repr_stats(net.queue.t().contiguous(), self.t)
         out["seconds"] = time.perf_counter() - t0
         return out
+
+    def run_epoch(self, model, loaders: tuple, ctx: dict) -> dict:
+        """The statistics of the queue -- and, as "bank", of the bank features when the kNN monitor has just left them in ctx."""
+        r = self.run(model)
+        r["dim"] = getattr(model, "module", model).queue.shape[0]
+        bank = ctx.pop("bank_features", None)
+        if bank is not None:
+            r["bank"] = dict(repr_stats(bank, self.t), dim=bank.shape[1])
+        return r
+
+    def scalars(self, result: dict) -> dict:
+        rec = {f"repr/{k}": result[k] for k in ("uniformity", "mean_cos", "effective_rank", "dim_std_min", "bad_rows")}
+        if "bank" in result:
+            rec.update({f"repr/bank_{k}": result["bank"][k] for k in ("uniformity", "effective_rank", "dim_std_min")})
+        return rec
+
+    def log_line(self, result: dict, ctx: dict) -> str:
+        r = result
+        line = (f"Repr [{ctx['epoch']}/{ctx['num_epochs']}]\tuniformity {r['uniformity']:.4f}\teff.rank "
+                f"{r['effective_rank']:.1f}/{r['dim']}\tmean cos {r['mean_cos']:.4f}\tdim std min "
+                f"{r['dim_std_min']:.3f}\t(t={self.t}, {r['rows']} rows, {r['bad_rows']} bad, {r['seconds']:.2f} s)")
+        if "bank" in r:
+            b = r["bank"]
+            line += f"\tbank: uniformity {b['uniformity']:.4f}\teff.rank {b['effective_rank']:.1f}/{b['dim']}"
+        return line
 
 
 # ---- command line over saved retrieval features --------------------------------------------------------------------------

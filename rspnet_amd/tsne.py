@@ -40,6 +40,8 @@ from torch import Tensor, nn
 from . import _lib
 from . import knn as _knn
 from . import ops as _ops
+from .framework.monitor import EpochMonitor
+from .knn import _rows, _valid_rows_np, _valid_rows_torch
 
 logger = logging.getLogger(__name__)
 MAX_ROWS, MAX_D, MAX_PERPLEXITY, MAX_ITERS, CALIB_STEPS = 16384, 4096, 1024.0, 10000, 64
@@ -71,16 +73,10 @@ def schedule(iters: int, lr: float, exag: float = 12.0, exag_iters: int = 250, m
 
 
 # ---- the definition in numpy fp64 ----------------------------------------------------------------------------------------
-def valid_rows(x32: np.ndarray) -> np.ndarray:
-    with np.errstate(all="ignore"):
-        ss = (x32 * x32).sum(axis=1, dtype=np.float32)
-        return np.isfinite(ss) & (ss > 0)
-
-
 def reference_distances(x) -> tuple:
     """(rows, d): the list of valid rows and the M x M fp64 distances of the rule (diagonal 0)."""
     x32 = np.asarray(x, dtype=np.float32)
-    rows = np.flatnonzero(valid_rows(x32))
+    rows = np.flatnonzero(_valid_rows_np(x32))
     a = x32[rows].astype(np.float64)
     a = a / np.linalg.norm(a, axis=1, keepdims=True)
     d = np.maximum(2.0 - 2.0 * (a @ a.T), 0.0)
@@ -169,11 +165,6 @@ def tsne_reference(x, perplexity, sched, y0, iters: int, keep=(), aff: Optional[
 
 
 # ---- the same rule from torch ops (any device; stores the M x M matrices: this is what a backend without the entry points runs) --
-def _valid_rows_torch(x: Tensor) -> Tensor:
-    ss = (x * x).sum(dim=1)
-    return torch.isfinite(ss) & (ss > 0)
-
-
 def affinities_torch(x: Tensor, perplexity: float):
     """(rows int64 (M,), d, beta, p, plogp, psum) in fp32 torch ops on x's device."""
     rows = torch.nonzero(_valid_rows_torch(x)).reshape(-1)
@@ -221,13 +212,6 @@ def step_torch(p: Tensor, plogp: float, y: Tensor, inc: Tensor, gains: Tensor, l
 
 
 # ---- the public calls ----------------------------------------------------------------------------------------------------
-def _rows(x: Tensor) -> Tensor:
-    x = x.to(torch.float32)
-    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) % 2):
-        x = x.contiguous()
-    return x
-
-
 def read_info(info: Tensor) -> dict:
     """The 32-byte rsp_tsne_info of HipOps.tsne_affinities as a dict (one small copy to the host)."""
     rec = _lib.TsneInfo.from_buffer_copy(info.cpu().numpy().tobytes())
@@ -344,68 +328,36 @@ def draw(y, labels, size: int = 512):
 
 
 # ---- the pretext driver's hook -------------------------------------------------------------------------------------------
-class TsneMonitor:
+class TsneMonitor(EpochMonitor):
     """Every ``every``-th epoch (and on the last one): the t-SNE map of the backbone features of a labelled bank from one encoder of the
     pretext model (``knn.extract``), written as ``tsne_epoch{E}.png`` / ``.npy``, with its final KL and its neighbour purity.  ``run``
     leaves the model as it found it -- state_dict() bit for bit, every module's ``training`` flag --, draws from no global random
-    generator and refuses to run inside a graph capture.  Has run on one GPU only."""
+    generator and refuses to run inside a graph capture.  Has run on one GPU only.  Config, e.g. {"every": 10, "perplexity": 30,
+    "iters": 500}."""
 
+    KEY = "tsne_monitor"
     KEYS = ("every", "perplexity", "iters", "encoder", "bank_samples", "batch_size", "n_crop", "seed")
     NUM_CLASSES = 10      # of the stand-in bank
 
     def __init__(self, every: int, num_epochs: int, perplexity: float = 30.0, iters: int = 500, encoder: str = "q", bank_samples: int = 256,
                  batch_size: int = 32, n_crop: int = 1, seed: int = 0):
-        if encoder not in ("q", "k"):
-            raise ValueError(f"tsne_monitor: encoder must be 'q' or 'k', got {encoder!r}")
-        if int(every) < 1 or min(int(bank_samples), int(batch_size), int(n_crop)) < 1:
-            raise ValueError("tsne_monitor: every, bank_samples, batch_size and n_crop must be at least 1")
+        self._check_encoder(encoder)
+        self._check_at_least_1(every=every, bank_samples=bank_samples, batch_size=batch_size, n_crop=n_crop)
         check_limits(bank_samples, 2, perplexity, iters)
         self.every, self.num_epochs, self.perplexity, self.iters = int(every), int(num_epochs), float(perplexity), int(iters)
         self.encoder, self.bank_samples, self.batch_size = encoder, int(bank_samples), int(batch_size)
         self.n_crop, self.seed = int(n_crop), int(seed)
 
-    @classmethod
-    def from_config(cls, cfg, num_epochs: int) -> Optional["TsneMonitor"]:
-        """The ``tsne_monitor`` key of a pretext config, e.g. {"every": 10, "perplexity": 30, "iters": 500}; None -- nothing
-        constructed, no launch ever added -- when the key is absent or ``every`` is 0."""
-        node = cfg.get("tsne_monitor") if hasattr(cfg, "get") else None
-        if not node:
-            return None
-        extra = sorted(set(node) - set(cls.KEYS))
-        if extra:
-            raise ValueError(f"tsne_monitor: unknown keys {extra}")
-        if int(node.get("every", 0)) <= 0:
-            return None
-        return cls(num_epochs=num_epochs, **{key: node[key] for key in cls.KEYS if key in node})
-
-    def due(self, epoch: int) -> bool:
-        """``epoch``: the 0-based epoch that has just finished its last step."""
-        return (int(epoch) + 1) % self.every == 0 or int(epoch) + 1 == self.num_epochs
-
-    def build_loader(self, T: int, size: int, device, seed: int = 0):
+    def build_loaders(self, T: int, size: int, device, seed: int = 0) -> tuple:
         """The kNN monitor's stand-in bank: split 'train' of ``SyntheticLabelledClips``."""
-        return _knn.synthetic_loaders(self.bank_samples, 1, self.batch_size, self.NUM_CLASSES, self.n_crop, T, size, device, seed)[0]
+        return _knn.synthetic_loaders(self.bank_samples, 1, self.batch_size, self.NUM_CLASSES, self.n_crop, T, size, device, seed)[:1]
 
     def run(self, model: nn.Module, bank_loader: Iterable, out_prefix: Optional[str] = None, image_size: int = 512) -> dict:
         """{"kl", "purity", "n_bank", "bad_rows", "seconds"}; with ``out_prefix`` the map goes to out_prefix + ".npy" and ".png"."""
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("TsneMonitor.run: never inside a graph capture")
+        self._refuse_capture()
         t0 = time.perf_counter()
-        net = getattr(model, "module", model)
-        enc = net.encoder_q if self.encoder == "q" else net.encoder_k
-        device = next(enc.parameters()).device
-        flags = [(m, m.training) for m in net.modules()]
-        try:
-            net.eval()
-            if self.encoder == "q" and hasattr(net, "_check_q_weights"):      # as knn.extract_bank_and_query
-                if not net._q_params:
-                    net._q_params = list(net.encoder_q.parameters())
-                net._check_q_weights()
-            n_crop = 1 if getattr(bank_loader, "split", None) == "train" else self.n_crop
-            g, y_g = _knn.extract(enc, bank_loader, device, n_crop)
-        finally:
-            for m, was in flags:
-                m.training = was
+        with _knn.frozen_encoder(model, self.encoder) as enc:
+            g, y_g = _knn.extract_bank(enc, bank_loader, self.n_crop)
         with torch.no_grad():
             perp = min(self.perplexity, max(1.0, (g.shape[0] - 1) / 3.0))
             res = fit(g, perp, self.iters, exag_iters=min(250, self.iters // 2), seed=self.seed)
@@ -415,6 +367,18 @@ class TsneMonitor:
             draw(ymap, lab, image_size).save(out_prefix + ".png")
         return {"kl": float(res.kl_trace[-1]), "purity": neighbour_purity(ymap, lab, 10), "n_bank": int(g.shape[0]),
                 "bad_rows": res.info["rows_bad"], "seconds": time.perf_counter() - t0}
+
+    def run_epoch(self, model, loaders: tuple, ctx: dict) -> dict:
+        """The map goes to tsne_epoch{E}.npy / .png in the run directory."""
+        return self.run(model, *loaders, os.path.join(ctx["run_dir"], f"tsne_epoch{ctx['epoch']}"))
+
+    def scalars(self, result: dict) -> dict:
+        return {"tsne_kl": result["kl"], "tsne_purity": result["purity"]}
+
+    def log_line(self, result: dict, ctx: dict) -> str:
+        r = result
+        return (f"t-SNE [{ctx['epoch']}/{ctx['num_epochs']}]\tKL {r['kl']:.4f}\tpurity@10 {r['purity']:.4f}"
+                f"\t(perplexity {self.perplexity:g}, {self.iters} iterations, bank {r['n_bank']}, {r['bad_rows']} bad, {r['seconds']:.1f} s)")
 
 
 # ---- command line over saved retrieval features --------------------------------------------------------------------------

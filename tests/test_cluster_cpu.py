@@ -4,7 +4,6 @@ monitor's configuration, the driver wiring and the command-line tool."""
 import ctypes
 import json
 import random
-import types
 
 import numpy as np
 import pytest
@@ -309,47 +308,3 @@ def test_command_line_tool(cpu_backend, tmp_path, caplog):
     out = cluster.main(["--features", str(tmp_path), "--fold", "2", "--split", "test", "--clusters", "6", "--iters", "7", "--seed", "2"])
     assert (out["split"], out["clusters"], out["max_iters"], out["seed"], out["restarts"], out["n"]) == ("test", 6, 7, 2, 1, 90)
     assert out["iters"] <= 7
-
-
-def test_pretext_driver_wiring_without_a_device(tmp_path):
-    """The driver's two methods on a stand-in engine (the driver itself binds to the device; its end-to-end run is a GPU test): the
-    monitor runs when due and only then, on rank 0 only, its six scalars go into that epoch's line and into no other, and the line's
-    other numbers are what they are without the monitor."""
-    from rspnet_amd.pretrain import Engine
-
-    class Mon:
-        num_clusters, calls = 5, []
-
-        def due(self, epoch):
-            return epoch % 2 == 1
-
-        def run(self, model, bank):
-            Mon.calls.append((model, bank))
-            return {"nmi": 0.5, "ari": 0.25, "purity": 0.75, "objective": 0.9, "iters": 7, "empty": 1, "n_bank": 24, "bad_rows": 0,
-                    "seconds": 0.1}
-
-    stats = {k: {"avg": float(i)} for i, k in enumerate(("loss", "loss_A", "acc1_A", "acc5_A", "loss_M", "acc1_M"))}
-
-    def engine(mon, rank=0, name="with"):
-        return types.SimpleNamespace(cluster=mon, cluster_loader="bank", _cluster_result=None, _probe_result=None, _knn_result=None,
-                                     _repr_result=None, local_rank=rank, current_epoch=0, num_epochs=2, model="model", stats=stats,
-                                     scalars_path=tmp_path / f"{name}.jsonl")
-    for name, mon in (("with", Mon()), ("without", None)):
-        e = engine(mon, name=name)
-        for epoch in range(2):
-            e.current_epoch = epoch
-            Engine._run_cluster_monitor(e)
-            Engine._write_scalars(e, 0.05)
-    lines = {name: [json.loads(l) for l in open(tmp_path / f"{name}.jsonl")] for name in ("with", "without")}
-    assert Mon.calls == [("model", "bank")]
-    first, second = lines["with"]
-    assert not any(k.startswith("cluster_") for k in first)
-    assert {k: v for k, v in second.items() if k.startswith("cluster_")} == {
-        "cluster_nmi": 0.5, "cluster_ari": 0.25, "cluster_purity": 0.75, "cluster_objective": 0.9, "cluster_iters": 7, "cluster_empty": 1}
-    assert not any(k.startswith("cluster_") for rec in lines["without"] for k in rec)
-    for a, b in zip(lines["with"], lines["without"]):
-        assert {k: v for k, v in a.items() if not k.startswith("cluster_")} == b
-    other = engine(Mon(), rank=1)
-    other.current_epoch = 1
-    Engine._run_cluster_monitor(other)
-    assert other._cluster_result is None and len(Mon.calls) == 1

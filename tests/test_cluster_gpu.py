@@ -157,28 +157,31 @@ def test_empty_clusters_keep_their_centroids():
 
 # ---- 6. non-finite values and invalid rows ---------------------------------------------------------------------------------------
 def test_invalid_rows_take_part_in_nothing():
-    """A zero row, a row with a NaN and a row with an Inf: assign -1, counted in rows_bad, and every output of the fit is, to the bit,
+    """Zero rows, rows with a NaN and rows with an Inf (255 and 256: the last lane of one 256-row trip of the compaction and the first of
+    the next): assign -1, counted in rows_bad, and every output of the fit is, to the bit,
     that of the fit on x without them."""
     x, _ = feats(3, 300, 34, 5, 1.0)
     x = np.array(x)
-    bad = [0, 63, 64, 299]
+    bad = [0, 63, 64, 255, 256, 299]
     x[0] = 0
     x[63, 33] = np.nan
     x[64, 0] = np.inf
+    x[255, 1] = np.nan
+    x[256] = 0
     x[299, 7] = -np.inf
     init = x[[5, 50, 100, 150, 200]].copy()
     got, gi, gc = run_fit(dev(x), init, 30)
     want, wi, wc = run_fit(dev(np.delete(x, bad, axis=0)), init, 30)
-    assert gi["rows_bad"] == 4 and gi["rows_valid"] == 296 and wi["rows_bad"] == 0
+    assert gi["rows_bad"] == 6 and gi["rows_valid"] == 294 and wi["rows_bad"] == 0
     assert {k: v for k, v in gi.items() if k != "rows_bad"} == {k: v for k, v in wi.items() if k != "rows_bad"}
-    assert got.assign[bad].tolist() == [-1] * 4
+    assert got.assign[bad].tolist() == [-1] * 6
     keep = np.delete(np.arange(300), bad)
     assert torch.equal(got.assign[keep], want.assign) and torch.equal(got.counts, want.counts) and torch.equal(got.changed, want.changed)
     assert torch.equal(bits(gc), bits(wc)) and torch.equal(bits(got.objective), bits(want.objective))
     ref = cluster.kmeans_reference(x, init, 30)
     assert gi["rows_valid"] == ref.info["rows_valid"] and gi["unassigned"] == 0
     a, sim = ops.backend().kmeans_assign(dev(x), gc)
-    assert a[bad].tolist() == [-1] * 4 and bool(torch.isnan(sim[bad]).all()) and torch.equal(a, got.assign)
+    assert a[bad].tolist() == [-1] * 6 and bool(torch.isnan(sim[bad]).all()) and torch.equal(a, got.assign)
 
 
 def test_a_nan_centroid_is_never_assigned():
@@ -354,7 +357,7 @@ def test_monitor_run_leaves_the_model_and_the_generators_alone():
     net.train()
     net.encoder_k.eval()                                   # a mixed set of flags: every module gets its own back
     mon = cluster.ClusterMonitor(every=1, num_epochs=1, num_clusters=3, num_classes=3, bank_samples=24, batch_size=4, max_iters=20)
-    bank = mon.build_loader(16, 32, DEV, seed=0)
+    (bank,) = mon.build_loaders(16, 32, DEV, seed=0)
     before = {n: t_.clone() for n, t_ in net.state_dict().items()}
     flags = [m.training for m in net.modules()]
     states = (random.getstate(), torch.get_rng_state().clone(), torch.cuda.get_rng_state(DEV).clone())

@@ -244,46 +244,3 @@ def test_command_line_tool(cpu_backend, tmp_path, caplog):
     out = linear_probe.main(["--features", str(tmp_path), "--fold", "2", "--steps", "10", "--batch", "64", "--lr", "0.05", "--wd", "0",
                              "--scale", "4", "--no-normalize"])
     assert (out["steps"], out["batch"], out["lr"], out["weight_decay"], out["scale"], out["normalize"]) == (10, 64, 0.05, 0.0, 4.0, False)
-
-
-def test_pretext_driver_wiring_without_a_device(tmp_path):
-    """The driver's two methods on a stand-in engine (the driver itself binds to the device; its end-to-end run is a GPU test): the
-    monitor runs when due and only then, on rank 0 only, its three scalars go into that epoch's line and into no other, and the
-    line's other numbers are what they are without the monitor."""
-    import types
-    from rspnet_amd.pretrain import Engine
-
-    class Mon:
-        steps, lr, calls = 20, 0.125, []
-
-        def due(self, epoch):
-            return epoch % 2 == 1
-
-        def run(self, model, bank, query):
-            Mon.calls.append((model, bank, query))
-            return {"acc1": 50.0, "acc5": 75.0, "loss": 1.25, "train_loss": 0.5, "n_bank": 24, "n_query": 12, "bad_rows": 0, "seconds": 0.1}
-
-    stats = {k: {"avg": float(i)} for i, k in enumerate(("loss", "loss_A", "acc1_A", "acc5_A", "loss_M", "acc1_M"))}
-
-    def engine(probe, rank=0, name="with"):
-        return types.SimpleNamespace(probe=probe, probe_loaders=("bank", "query"), _probe_result=None, _knn_result=None, _repr_result=None,
-                                     local_rank=rank, current_epoch=0, num_epochs=2, model="model", stats=stats,
-                                     scalars_path=tmp_path / f"{name}.jsonl")
-    for name, probe in (("with", Mon()), ("without", None)):
-        e = engine(probe, name=name)
-        for epoch in range(2):
-            e.current_epoch = epoch
-            Engine._run_probe_monitor(e)
-            Engine._write_scalars(e, 0.05)
-    lines = {name: [json.loads(l) for l in open(tmp_path / f"{name}.jsonl")] for name in ("with", "without")}
-    assert Mon.calls == [("model", "bank", "query")]
-    first, second = lines["with"]
-    assert not any(k.startswith("probe_") for k in first)
-    assert {k: v for k, v in second.items() if k.startswith("probe_")} == {"probe_acc1": 50.0, "probe_acc5": 75.0, "probe_loss": 1.25}
-    assert not any(k.startswith("probe_") for rec in lines["without"] for k in rec)
-    for a, b in zip(lines["with"], lines["without"]):
-        assert {k: v for k, v in a.items() if not k.startswith("probe_")} == b
-    other = engine(Mon(), rank=1)
-    other.current_epoch = 1
-    Engine._run_probe_monitor(other)
-    assert other._probe_result is None and len(Mon.calls) == 1

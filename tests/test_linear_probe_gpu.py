@@ -188,16 +188,20 @@ def test_guarded_memory(case):
 
 
 def test_invalid_rows_take_part_in_nothing():
-    """A zero row, a row with a NaN, a row with an Inf and the labels -1 and C, with batch = N: W, b and loss_trace are, to the bit,
+    """A zero row, a row with a NaN, a row with an Inf and the labels -1 and C -- rows 255 and 256, the last lane of one 256-row trip of
+    the compaction and the first lane of the next, among them --, with batch = N: W, b and loss_trace are, to the bit,
     those of the fit on the array without the rows -- on both paths; counts says how many there were; their logits are NaN."""
     N, D, C = 300, 34, 7
     x, y, _, _ = case_inputs(N, D, C)
     x, y = np.array(x), np.array(y)
-    bad = [0, 63, 64, 200, N - 1]
+    bad = [0, 63, 64, 200, 255, 256, N - 1]
+    nb = len(bad)
     x[0] = 0
     x[63, D - 1] = np.nan
     x[64, 0] = np.inf
     y[200] = -1
+    x[255, 1] = -np.inf
+    y[256] = -1
     y[N - 1] = C
     ref = linear_probe.probe_reference(x, y, C, linear_probe.lr_schedule(0.125, 100), 100, N)
     for forced in (False, True):
@@ -205,18 +209,18 @@ def test_invalid_rows_take_part_in_nothing():
             os.environ["RSP_PROBE_GENERAL"] = "1"
         try:
             got = fit_from_zeros(dev(x), dev(y), C, N, 100)
-            want = fit_from_zeros(dev(np.delete(x, bad, axis=0)), dev(np.delete(y, bad)), C, N - 5, 100)
+            want = fit_from_zeros(dev(np.delete(x, bad, axis=0)), dev(np.delete(y, bad)), C, N - nb, 100)
         finally:
             os.environ.pop("RSP_PROBE_GENERAL", None)
-        assert got[4].tolist() == [N - 5, 5] and want[4].tolist() == [N - 5, 0]
+        assert got[4].tolist() == [N - nb, nb] and want[4].tolist() == [N - nb, 0]
         for a, b in zip(got[:4], want[:4]):
             assert torch.equal(bits(a), bits(b))
-        check(got[0].cpu().numpy(), got[1].cpu().numpy(), got[3].cpu().numpy(), ref, f"five invalid rows (general: {forced})")
+        check(got[0].cpu().numpy(), got[1].cpu().numpy(), got[3].cpu().numpy(), ref, f"seven invalid rows (general: {forced})")
     probe = linear_probe.Probe(got[0], got[1], got[3], got[4], True, 8.0)
     z = linear_probe.logits(probe, dev(x))
-    assert torch.isnan(z).any(dim=1).nonzero().reshape(-1).tolist() == [0, 63, 64] and bool(torch.isnan(z[[0, 63, 64]]).all())
+    assert torch.isnan(z).any(dim=1).nonzero().reshape(-1).tolist() == [0, 63, 64, 255] and bool(torch.isnan(z[[0, 63, 64, 255]]).all())
     res = linear_probe.evaluate(probe, dev(x), dev(y))
-    assert res["hits"][0] == N - 5 and res["rank"][bad].tolist() == [C] * 5
+    assert res["hits"][0] == N - nb and res["rank"][bad].tolist() == [C] * nb
     # a chunk without a valid row: loss 0, only the weight decay moves the state
     w0, b0 = torch.full((C, D), 0.5, device=DEV), torch.full((C,), -0.25, device=DEV)
     out = fit_from_zeros(dev(x), torch.full((N,), C, dtype=torch.int64, device=DEV), C, N, 2, state=(w0, b0, torch.zeros(C * D + C, device=DEV)),

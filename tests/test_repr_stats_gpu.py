@@ -95,18 +95,20 @@ def test_guarded_memory(N, D):
 def test_invalid_rows_take_part_in_nothing():
     N, D = 300, 70
     x = np.array(case_input(N, D))
-    bad = [0, 63, 64, 200, 299]
+    bad = [0, 63, 64, 200, 255, 256, 299]      # (255, 256: the last row of one 256-row stretch and the first of the next)
     x[0] = 0
     x[63, 69] = np.nan
     x[64, 0] = np.inf
     x[200] = np.nan
+    x[255, 5] = np.inf
+    x[256] = 0
     x[299, 31] = -np.inf
     ref = repr_stats.repr_reference(np.delete(x, bad, axis=0))
     got = raw(ops.backend().repr_stats(torch.from_numpy(x).to(DEV), 2.0))
-    assert (got["rows_valid"], got["rows_bad"]) == (N - 5, 5)
-    check(dict(got, rows_bad=0), ref, "five invalid rows")
+    assert (got["rows_valid"], got["rows_bad"]) == (N - 7, 7)
+    check(dict(got, rows_bad=0), ref, "seven invalid rows")
     out = repr_stats.repr_stats(torch.from_numpy(x).to(DEV))
-    assert (out["rows"], out["bad_rows"]) == (N - 5, 5) and all(np.isfinite(v) for v in out.values())
+    assert (out["rows"], out["bad_rows"]) == (N - 7, 7) and all(np.isfinite(v) for v in out.values())
     # fewer than two valid rows: the sums are zero, the uniformity is NaN
     one = repr_stats.repr_stats(torch.from_numpy(x[[0, 1, 200]]).to(DEV))
     assert np.isnan(one["uniformity"]) and np.isnan(one["mean_cos"]) and (one["rows"], one["bad_rows"]) == (1, 2)

@@ -154,12 +154,21 @@ def test_whole_fit_separates_the_clusters():
 
 # ---- 5. invalid rows ---------------------------------------------------------------------------------------------------------------
 def test_invalid_rows_take_part_in_nothing():
-    N, D, iters = 132, 34, 4
-    x, _ = tu.clusters(9, 3, 44, D, 0.5)
-    bad = [0, 70, 131]
-    x[0] = 0
-    x[70, 3] = np.nan
-    x[131, 5] = np.inf
+    invalid_rows_case(132, [0, 70, 131])      # one 256-row trip of the compaction
+
+
+def test_invalid_rows_take_part_in_nothing_over_two_trips():
+    invalid_rows_case(300, [0, 63, 64, 255, 256, 299])      # (255, 256: the last lane of the first trip, the first lane of the second)
+
+
+def invalid_rows_case(N, bad):
+    D, iters = 34, 4
+    x, _ = tu.clusters(9, 3, N // 3, D, 0.5)
+    for n, i in enumerate(bad):      # a zero row, a row with a NaN, a row with an Inf, in turn
+        if n % 3 == 0:
+            x[i] = 0
+        else:
+            x[i, 3 if n % 3 == 1 else 5] = np.nan if n % 3 == 1 else np.inf
     good = np.delete(np.arange(N), bad)
     rng = np.random.default_rng(2)
     y0 = (rng.standard_normal((N, 2)) * 1e-4).astype(np.float32)
@@ -176,9 +185,9 @@ def test_invalid_rows_take_part_in_nothing():
         kl = be.tsne_fit(aff, sched, 0, iters, y, inc, gains)
         outs.append((aff, tsne.read_info(aff.info), y, inc, gains, kl))
     (fa, fi, fy, finc, fg, fkl), (ca, ci, cy, cinc, cg, ckl) = outs
-    M = N - 3
-    assert fi["rows_valid"] == M and fi["rows_bad"] == 3 and ci["rows_valid"] == M and ci["rows_bad"] == 0
-    assert fa.rows.cpu().tolist() == list(good) + [-1] * 3 and (fi["plogp"], fi["psum"]) == (ci["plogp"], ci["psum"])
+    M = N - len(bad)
+    assert fi["rows_valid"] == M and fi["rows_bad"] == len(bad) and ci["rows_valid"] == M and ci["rows_bad"] == 0
+    assert fa.rows.cpu().tolist() == list(good) + [-1] * len(bad) and (fi["plogp"], fi["psum"]) == (ci["plogp"], ci["psum"])
     assert torch.equal(bits(fa.pmat[:M, :M]), bits(ca.pmat)) and torch.equal(bits(fa.dmat[:M, :M]), bits(ca.dmat))
     assert torch.equal(bits(fa.beta[:M]), bits(ca.beta)) and bool(torch.isnan(fa.beta[M:]).all())
     assert bool((fa.pmat[M:] == 0).all()) and bool((fa.pmat[:, M:] == 0).all())
@@ -293,7 +302,7 @@ def test_monitor_run_leaves_the_model_and_the_generators_alone(tmp_path):
     net.train()
     net.encoder_k.eval()
     mon = tsne.TsneMonitor(every=1, num_epochs=1, perplexity=5, iters=40, bank_samples=24, batch_size=4)
-    bank = mon.build_loader(16, 32, DEV, seed=0)
+    (bank,) = mon.build_loaders(16, 32, DEV, seed=0)
     before = {n: t_.clone() for n, t_ in net.state_dict().items()}
     flags = [m.training for m in net.modules()]
     states = (random.getstate(), torch.get_rng_state().clone(), torch.cuda.get_rng_state(DEV).clone())
